@@ -23,12 +23,22 @@ line whose `levels` list carries the per-level iteration time, kernel shares and
 `--config 3 --emulate-rank-of R` runs, on ONE GPU, the full window AND one rank's 1/R shard through the multi-rank code
 path (peer exchange at world = 1) and prints the projected R-GPU speed-up; --config 4 is configs[4] (11x11 patches +
 Huber 0.05, weak scaling like configs[1]).
+
+A plain run sets up, warms up, times EXACTLY --steps LM iterations once and prints the line.  --full adds everything else: the
+timed solve repeated --repeats (default 25) times with the median reported, the `roofline` object (one more profiled solve), the
+PCIe-inclusive upload, the device-copy bandwidth, the `exchange` figures, the `strong` record at N > 1 and the CPU baselines.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed solve hands its caller -- cams.npy, xyz.npy (the refined
+state) and iterations.npy (one row per LM iteration: ITERATION_COLUMNS) -- as float64 .npy files, at most DUMP_BYTES in all (a
+seeded sample of the rows of a larger array).  The inputs are seeded, so two builds run with the same arguments can be compared
+array for array.  At N > 1 every rank writes its own files (suffix _rank<r>); --config 2 writes one set per level (prefix level<k>_).
 """
 import argparse
 import hashlib
 import json
 import os
 import sys
+import threading
 import time
 
 import numpy as np
@@ -38,6 +48,30 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK = 8.0e12   # bytes/s, MI355X HBM3E spec (MI355X_MICROARCH.md)
+DUMP_BYTES = 48 << 20   # --dump-outputs: bound of all arrays a run writes (all ranks together)
+ITERATION_COLUMNS = ("iteration", "cost", "cost_change", "gradient_max_norm", "gradient_norm", "step_norm", "relative_decrease",
+                     "trust_region_radius", "step_is_valid", "step_is_successful")
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: every array as <path>/<name>.npy in float64.  An array beyond its share of `budget` keeps a fixed, seeded
+    sample of its rows (sorted), so that runs with the same arguments write the same rows."""
+    os.makedirs(path, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.nbytes > share and a.ndim > 0:
+            keep = max(1, share // max(1, a[:1].nbytes))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def solve_outputs(eng, res, prefix=""):
+    """What a caller of the timed path receives from the last solve: the refined state (still on the device after pba_solve) and
+    the iteration log (wall-clock fields left out: they differ from run to run)."""
+    cams, xyz = eng.get_state()
+    its = np.array([[float(i[k]) for k in ITERATION_COLUMNS] for i in res["iterations"]], dtype=np.float64).reshape(-1, len(ITERATION_COLUMNS))
+    return {prefix + "cams": cams, prefix + "xyz": xyz, prefix + "iterations": its}
 
 
 def algorithmic_bytes(radius, n_bar, channels=1):
@@ -119,6 +153,7 @@ def bench_pyramid(args):
     raw_buffers = Engine.solve_buffers()
     out_levels, total_s, total_bytes = [], 0.0, 0.0
     engines = []
+    dumps = {}
     for L in levels:
         prob = L["prob"]
         eng = Engine(L["rows"], L["cols"], prob.K, prob.radius, prob.n_frames, huber=prob.huber, device=0)
@@ -139,6 +174,8 @@ def bench_pyramid(args):
             torch.cuda.synchronize()
             times.append(time.perf_counter() - t1)
             res = Engine.unpack_solve(*raw)
+        if args.dump_outputs:
+            dumps.update(solve_outputs(eng, res, "level%d_" % L["level"]))
         times.sort()
         el = times[len(times) // 2]
         iters = len(res["iterations"]) - 1
@@ -208,6 +245,8 @@ def bench_pyramid(args):
                      "whole_pass_frac": (total_bytes / total_s) / HBM_PEAK, "kernel_source_id": kernel_source_id(), "traffic_matches_build": None},
         "gen_seconds": t_gen,
     }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dumps)
     print(json.dumps(out))
     for e_ in engines:
         e_.close()
@@ -235,9 +274,15 @@ def main():
                          "3 IntensityAndGradient, 8 BitPlanes")
     ap.add_argument("--inverse-depth", action="store_true",
                     help="the north star's SE(3) x inverse-depth parameterisation (pba_set_inverse_depth; no reference counterpart)")
-    ap.add_argument("--repeats", type=int, default=25,
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: repeated timing (--repeats), roofline, PCIe-inclusive upload, device-copy "
+                         "bandwidth, exchange figures, the strong record at N > 1 and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed solve returns (cams, xyz, iteration log) as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the K-step solve is timed this many times (each bracketed by barrier + synchronize, state reset outside "
-                         "the bracket); `value` / `ms_per_step` come from the MEDIAN repeat, min / max are reported beside it")
+                         "the bracket); `value` / `ms_per_step` come from the MEDIAN repeat, min / max are reported beside it "
+                         "(default: 1, with --full 25)")
     ap.add_argument("--emulate-rank-of", type=int, default=0,
                     help="with --config 3 on ONE GPU: time the full window (single-rank path), then one rank's 1/R shard through the "
                          "multi-rank code path (PBA_FORCE_MULTI: reduction -> mailbox -> solve with the peer wait, k_decide with the peer "
@@ -250,6 +295,8 @@ def main():
     ap.add_argument("--cpu-points", type=int, default=50000, help="points of the bounded CPU-baseline sample")
     ap.add_argument("--cpu-steps", type=int, default=20)
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 25 if args.full else 1
     if args.config == 2:
         return bench_pyramid(args)
     preset = {1: dict(frames=8, points=50000, radius=2, huber=0.0), 3: dict(frames=16, points=200000, radius=2, huber=0.0),
@@ -263,12 +310,39 @@ def main():
     if emulate:
         args.no_cpu_baseline = True
 
-    import torch
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus > 1 and world != args.gpus:
         raise SystemExit("launch with torch.distributed.run --nproc-per-node %d (WORLD_SIZE=%d)" % (args.gpus, world))
+    from photobundle_amd import synthetic
+
+    # ---- synthetic window: identical frames/cameras on every rank, rank-specific points ----------------------
+    # (built on a thread of its own while torch and the device come up: numpy's loops release the GIL, the bits are the same)
+    default_shape = not explicit and (args.visibility, args.precision, args.channels, args.inverse_depth) == ("dense", "exact", 1, False)
+    ch_fn = synthetic.channel_fn({3: "IntensityAndGradient", 8: "BitPlanes"}[args.channels]) if args.channels > 1 else None
+    window = {}
+
+    def make_window():
+        t0 = time.time()
+        try:
+            if strong:
+                # the SAME window on every rank (same seeds), each rank keeps its contiguous shard of whole points
+                whole = synthetic.make_window(n_frames=args.frames, n_points=args.points, radius=args.radius, huber=args.huber,
+                                              visibility=args.visibility, dense_births=(0, 8) if args.frames > 8 else (0,), channel_fn=ch_fn)
+                window["prob"] = whole.shard(rank, world) if world > 1 else whole
+                del whole
+            else:
+                window["prob"] = synthetic.make_window(n_frames=args.frames, n_points=args.points, radius=args.radius, huber=args.huber,
+                                                       visibility=args.visibility, point_seed_offset=rank, channel_fn=ch_fn)
+        except BaseException as exc:      # re-raised on the main thread
+            window["error"] = exc
+        window["seconds"] = time.time() - t0
+
+    gen = threading.Thread(target=make_window, daemon=True)
+    gen.start()
+
+    import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU: the engine has no CPU fallback")
     # PBA_BENCH_BACKEND=gloo is a test hook: N ranks sharing the GPUs that exist (RCCL refuses duplicate devices, so
@@ -286,23 +360,13 @@ def main():
         else:
             dist.init_process_group(backend)
 
-    from photobundle_amd import synthetic
     from photobundle_amd.engine import Engine, default_solver_options
 
-    # ---- synthetic window: identical frames/cameras on every rank, rank-specific points ----------------------
-    t0 = time.time()
-    default_shape = not explicit and (args.visibility, args.precision, args.channels, args.inverse_depth) == ("dense", "exact", 1, False)
-    ch_fn = synthetic.channel_fn({3: "IntensityAndGradient", 8: "BitPlanes"}[args.channels]) if args.channels > 1 else None
-    if strong:
-        # the SAME window on every rank (same seeds), each rank keeps its contiguous shard of whole points
-        whole = synthetic.make_window(n_frames=args.frames, n_points=args.points, radius=args.radius, huber=args.huber,
-                                      visibility=args.visibility, dense_births=(0, 8) if args.frames > 8 else (0,), channel_fn=ch_fn)
-        prob = whole.shard(rank, world) if world > 1 else whole
-        del whole
-    else:
-        prob = synthetic.make_window(n_frames=args.frames, n_points=args.points, radius=args.radius, huber=args.huber,
-                                     visibility=args.visibility, point_seed_offset=rank, channel_fn=ch_fn)
-    t_gen = time.time() - t0
+    gen.join()
+    if "error" in window:
+        raise window["error"]
+    prob, t_gen = window["prob"], window["seconds"]
+    del window
     rows, cols = prob.images.shape[1:]
     P = prob.patch_len * args.channels          # residuals of one block
     n_obs_local = prob.n_obs
@@ -442,59 +506,15 @@ def main():
             elapsed = float(t.item())
         return elapsed, tot, res
 
-    # One K-step solve is a few milliseconds: it is repeated (same initial window every time, so every repeat runs the
-    # same iterations) and the MEDIAN repeat is the reported one; the whole timed region is repeats x K steps.
+    # A plain run times the K steps once.  With --full (or --repeats R) the K-step solve, a few milliseconds, is repeated (same
+    # initial window every time, so every repeat runs the same iterations) and the MEDIAN repeat is the reported one.
     runs = [timed_run() for _ in range(max(1, args.repeats))]
     times = sorted(r[0] for r in runs)
     elapsed = times[len(times) // 2] if len(times) % 2 else 0.5 * (times[len(times) // 2 - 1] + times[len(times) // 2])
     tot, res = runs[0][1], runs[0][2]
-    # PCIe-inclusive variant (never `value`): the C-ABI receives HOST buffers, so a cold window also pays the upload of
-    # all frames (u8), the problem (points, descriptors, observation lists) and the cameras before the same solve
-    barrier()
-    t2 = time.perf_counter()
-    for s_ in range(prob.n_frames):
-        if args.channels > 1:
-            eng.set_frame_channels(s_, prob.channel_images[s_])
-        else:
-            eng.set_frame(s_, prob.images[s_])
-    reset_state()
-    upload_s = time.perf_counter() - t2
-    # measured device-copy bandwidth (SURVEY.md 8d asks for it next to the 8 TB/s spec figure): 1 GiB device-to-device
-    copy_gbps = None
-    if rank == 0:
-        try:
-            src_t = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
-            dst_t = torch.empty_like(src_t)
-            dst_t.copy_(src_t)
-            torch.cuda.synchronize()
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-            for _ in range(5):
-                dst_t.copy_(src_t)
-            ev1.record()
-            torch.cuda.synchronize()
-            copy_gbps = 5 * 2.0 * (1 << 30) / (ev0.elapsed_time(ev1) * 1e-3) / 1e9     # read + write
-            del src_t, dst_t
-        except Exception:
-            copy_gbps = None
-    # per-kernel shares of the iteration: one more solve, outside the timed region.  Single rank: device time stamps inside
-    # the same asynchronous pipeline the timed region ran (interval between consecutive kernel ends; nothing is added to
-    # the stream -- an event record after every kernel makes it end with a cache write-back the pipelined run never pays,
-    # which inflated k_schur by ~6 us).  More ranks: HIP events around every kernel of the host-stepped driver, which also
-    # times the two per-step exchanges.
-    reset_state()
-    if world == 1:
-        eng.set_profiling(2)
-        eng.solve(opts(args.steps))
-        timing_source = "device time stamps in the asynchronous pipeline (interval between consecutive kernel ends)"
-        if eng.solve_driver() == "resident":
-            timing_source = ("phase stamps of the serial workgroup of the resident solve (one launch per solve): elimination | reduction + reduced "
-                             "solve | back-substitution + sampling + decision, reported under the names of the kernels that do this work on the pipelined path")
-    else:
-        eng.reset_counters()
-        eng.solve(opts(min(args.steps, 10)))
-        timing_source = "HIP events around every kernel of the host-stepped driver (each bracket ends with a cache write-back)"
-    ctr = eng.counters()
+    if args.dump_outputs:          # the refined state of the last timed solve is still the engine's
+        sfx = ("_rank%d" % rank) if world > 1 else ""
+        dump_outputs(args.dump_outputs, {k + sfx: v for k, v in solve_outputs(eng, runs[-1][2]).items()}, DUMP_BYTES // world)
 
     iters_done = tot["iters"]
     n_jac, n_cost, n_res = tot["n_jac"], tot["n_cost"], tot["n_res"]
@@ -502,68 +522,7 @@ def main():
     iters_per_sec = iters_done / elapsed
     value = iters_per_sec          # LM iterations per second of the ONE window the ranks solve together (never x N)
     residuals_per_sec = n_obs_global * P * (n_jac + n_cost) / elapsed   # residuals actually evaluated by the engine
-
-    ab = algorithmic_bytes(prob.radius, n_bar, args.channels)
-    # SURVEY.md 8d accounting rule, "with the actual pass counts of the run": the engine fuses the candidate cost pass into
-    # a speculative Jacobian pass, so a successful iteration is ONE Jacobian pass (and no cost pass); a rejected one is
-    # followed by a re-solve from the stored linearisation.
     n_succ = tot["n_succ"]
-    n_rej = iters_done - n_succ
-    run_bytes = n_obs_global * (n_jac * ab["b_jac"] + n_cost * ab["b_cost"] + n_res * ab["b_res"])
-    # ... and with the NOMINAL pass counts of the reference's algorithm for the same trace (iteration 0 = one Jacobian
-    # pass, a successful iteration = cost pass + Jacobian pass, a rejected one = cost pass + re-solve): reported beside it
-    run_bytes_nominal = n_obs_global * ((1 + n_succ) * ab["b_jac"] + iters_done * ab["b_cost"] + n_rej * ab["b_res"])
-    # dominant kernel, timed live with HIP events on the engine's stream (rank-local launch = local observations)
-    kern = {
-        "k_sample<JAC> (Jacobian pass)": (ctr["linearize_ms"], ctr["linearize_launches"], ab["sample_jac"]),
-        "k_sample<cost> (cost pass)": (ctr["cost_ms"], ctr["cost_launches"], ab["b_cost"]),
-        "k_schur (point elimination)": (ctr["schur_ms"], ctr["schur_launches"], ab["schur"]),
-        # serial stretch of the iteration: reduction of the Schur partials + reduced camera solve (O(frames^2): no per-observation bytes)
-        "k_reduce_solve (partials + reduced solve)": (ctr["solve_ms"], ctr["solve_launches"], 0.0),
-    }
-    # the kernel with the largest average launch duration (no tie-break; `per_kernel` carries the others)
-    avg_ms = {k: v[0] / max(1, v[1]) for k, v in kern.items()}
-    dom = max((k for k in kern if kern[k][2] > 0), key=lambda k: avg_ms[k])      # (the serial solve stage moves no per-observation bytes)
-    ms, launches, bytes_per_obs = kern[dom]
-    avg_s = (ms / max(1, launches)) * 1e-3
-    achieved = n_obs_local * bytes_per_obs / avg_s if avg_s > 0 else 0.0
-    # counter-based figures of the same kernel from the committed PMC passes (profiles/traffic.json, tools/collect_profiles.py):
-    # HBM-side bytes per launch (2 x FETCH_SIZE + WRITE_SIZE, calibration in profiles/r02/fetch_calibration.txt) and the
-    # VALU instruction count, which gives the issue floor: wave instructions x 4 cycles / (1024 SIMDs x 2.4 GHz)
-    traffic = valu_insts = None
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    traffic_sha = traffic_src_id = None
-    src_id = kernel_source_id()
-    if os.path.exists(tpath) and default_shape and args.config == 1:
-        try:
-            raw = open(tpath, "rb").read()
-            traffic_sha = hashlib.sha1(raw).hexdigest()[:12]
-            tj = json.loads(raw)
-            traffic = tj.get(dom.split(" ")[0])
-            valu_insts = tj.get(dom.split(" ")[0] + "_valu_insts")
-            traffic_src_id = tj.get("kernel_source_id")
-        except Exception:
-            traffic = valu_insts = None
-    roofline = {
-        "bound": "hbm", "kernel": dom, "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-        "frac": achieved / HBM_PEAK, "traffic": traffic,
-        "traffic_source": ("profiles/traffic.json sha1 %s (committed rocprofv3 --pmc passes of this workload; NOT measured in this run); "
-                           "counters taken on kernel sources %s, this build is %s: %s"
-                           % (traffic_sha, traffic_src_id, src_id, "MATCH" if traffic_src_id == src_id else "STALE counter file")
-                           if traffic else None),
-        "traffic_matches_build": (traffic_src_id == src_id) if traffic else None,
-        "kernel_source_id": src_id,
-        "traffic_frac": (traffic / avg_s / HBM_PEAK) if (traffic and avg_s > 0) else None,
-        "valu_floor_us": (valu_insts * 4.0 / (1024 * 2.4e9) * 1e6) if valu_insts else None,
-        "avg_launch_us": avg_s * 1e6, "timing_source": timing_source, "algorithmic_bytes_per_obs": bytes_per_obs,
-        "whole_iteration_frac": (run_bytes / elapsed) / (HBM_PEAK * world),
-        "whole_iteration_frac_nominal": (run_bytes_nominal / elapsed) / (HBM_PEAK * world),
-        "kernels_ms_per_launch": {k: (v[0] / max(1, v[1])) for k, v in kern.items()},
-        # the same figures for every timed kernel (the two big ones are within a few microseconds of each other)
-        "per_kernel": {k: {"avg_launch_us": 1e3 * v[0] / v[1], "algorithmic_bytes_per_obs": v[2],
-                           "frac": n_obs_local * v[2] / (1e-3 * v[0] / v[1]) / HBM_PEAK}
-                       for k, v in kern.items() if v[1] > 0 and v[0] > 0},
-    }
 
     out = {
         "metric": "LM iters/sec + residuals/sec, 8-frame KITTI window, 50k pts, 5x5 patch",
@@ -587,16 +546,129 @@ def main():
         "lm": {"iterations": iters_done, "successful": n_succ, "solves": -(-args.steps // CHUNK), "jacobian_passes": n_jac,
                "cost_passes": n_cost, "resolve_passes": n_res, "initial_cost": res["initial_cost"],
                "final_cost": res["final_cost"], "message": res["message"]},
-        "roofline": roofline,
-        "exchange": {"transport": eng.comm_transport(), "ranks_seen_by_transport": eng.comm_rank_count(),
-                     "us_per_step": (1e3 * ctr["exchange_ms"] / ctr["exchange_launches"]) if ctr["exchange_launches"] else 0.0,
-                     "note": "both per-step exchanges (packed reduced camera system + step scalars), HIP events on the engine's stream in the "
-                             "profiled (host-stepped) solve; 0 at one rank"},
-        "pcie_inclusive": {"upload_ms": 1e3 * upload_s, "iters_per_sec": iters_done / (elapsed + upload_s),
-                           "note": "host->device upload of the whole window (frames, points, descriptors, observations, cameras) + the same solve"},
-        "device_copy_GBps": copy_gbps,
         "gen_seconds": t_gen,
     }
+
+    # ---- --full: the figures that take runs of their own -------------------------------------------------------
+    if args.full:
+        # PCIe-inclusive variant (never `value`): the C-ABI receives HOST buffers, so a cold window also pays the upload of
+        # all frames (u8), the problem (points, descriptors, observation lists) and the cameras before the same solve
+        barrier()
+        t2 = time.perf_counter()
+        for s_ in range(prob.n_frames):
+            if args.channels > 1:
+                eng.set_frame_channels(s_, prob.channel_images[s_])
+            else:
+                eng.set_frame(s_, prob.images[s_])
+        reset_state()
+        upload_s = time.perf_counter() - t2
+        # measured device-copy bandwidth (SURVEY.md 8d asks for it next to the 8 TB/s spec figure): 1 GiB device-to-device
+        copy_gbps = None
+        if rank == 0:
+            try:
+                src_t = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
+                dst_t = torch.empty_like(src_t)
+                dst_t.copy_(src_t)
+                torch.cuda.synchronize()
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ev0.record()
+                for _ in range(5):
+                    dst_t.copy_(src_t)
+                ev1.record()
+                torch.cuda.synchronize()
+                copy_gbps = 5 * 2.0 * (1 << 30) / (ev0.elapsed_time(ev1) * 1e-3) / 1e9     # read + write
+                del src_t, dst_t
+            except Exception:
+                copy_gbps = None
+        # per-kernel shares of the iteration: one more solve, outside the timed region.  Single rank: device time stamps inside
+        # the same asynchronous pipeline the timed region ran (interval between consecutive kernel ends; nothing is added to
+        # the stream -- an event record after every kernel makes it end with a cache write-back the pipelined run never pays,
+        # which inflated k_schur by ~6 us).  More ranks: HIP events around every kernel of the host-stepped driver, which also
+        # times the two per-step exchanges.
+        reset_state()
+        if world == 1:
+            eng.set_profiling(2)
+            eng.solve(opts(args.steps))
+            timing_source = "device time stamps in the asynchronous pipeline (interval between consecutive kernel ends)"
+            if eng.solve_driver() == "resident":
+                timing_source = ("phase stamps of the serial workgroup of the resident solve (one launch per solve): elimination | reduction + reduced "
+                                 "solve | back-substitution + sampling + decision, reported under the names of the kernels that do this work on the pipelined path")
+        else:
+            eng.reset_counters()
+            eng.solve(opts(min(args.steps, 10)))
+            timing_source = "HIP events around every kernel of the host-stepped driver (each bracket ends with a cache write-back)"
+        ctr = eng.counters()
+
+        ab = algorithmic_bytes(prob.radius, n_bar, args.channels)
+        # SURVEY.md 8d accounting rule, "with the actual pass counts of the run": the engine fuses the candidate cost pass into
+        # a speculative Jacobian pass, so a successful iteration is ONE Jacobian pass (and no cost pass); a rejected one is
+        # followed by a re-solve from the stored linearisation.
+        n_rej = iters_done - n_succ
+        run_bytes = n_obs_global * (n_jac * ab["b_jac"] + n_cost * ab["b_cost"] + n_res * ab["b_res"])
+        # ... and with the NOMINAL pass counts of the reference's algorithm for the same trace (iteration 0 = one Jacobian
+        # pass, a successful iteration = cost pass + Jacobian pass, a rejected one = cost pass + re-solve): reported beside it
+        run_bytes_nominal = n_obs_global * ((1 + n_succ) * ab["b_jac"] + iters_done * ab["b_cost"] + n_rej * ab["b_res"])
+        # dominant kernel, timed live with HIP events on the engine's stream (rank-local launch = local observations)
+        kern = {
+            "k_sample<JAC> (Jacobian pass)": (ctr["linearize_ms"], ctr["linearize_launches"], ab["sample_jac"]),
+            "k_sample<cost> (cost pass)": (ctr["cost_ms"], ctr["cost_launches"], ab["b_cost"]),
+            "k_schur (point elimination)": (ctr["schur_ms"], ctr["schur_launches"], ab["schur"]),
+            # serial stretch of the iteration: reduction of the Schur partials + reduced camera solve (O(frames^2): no per-observation bytes)
+            "k_reduce_solve (partials + reduced solve)": (ctr["solve_ms"], ctr["solve_launches"], 0.0),
+        }
+        # the kernel with the largest average launch duration (no tie-break; `per_kernel` carries the others)
+        avg_ms = {k: v[0] / max(1, v[1]) for k, v in kern.items()}
+        dom = max((k for k in kern if kern[k][2] > 0), key=lambda k: avg_ms[k])      # (the serial solve stage moves no per-observation bytes)
+        ms, launches, bytes_per_obs = kern[dom]
+        avg_s = (ms / max(1, launches)) * 1e-3
+        achieved = n_obs_local * bytes_per_obs / avg_s if avg_s > 0 else 0.0
+        # counter-based figures of the same kernel from the committed PMC passes (profiles/traffic.json, tools/collect_profiles.py):
+        # HBM-side bytes per launch (2 x FETCH_SIZE + WRITE_SIZE, calibration in profiles/r02/fetch_calibration.txt) and the
+        # VALU instruction count, which gives the issue floor: wave instructions x 4 cycles / (1024 SIMDs x 2.4 GHz)
+        traffic = valu_insts = None
+        tpath = os.path.join(ROOT, "profiles", "traffic.json")
+        traffic_sha = traffic_src_id = None
+        src_id = kernel_source_id()
+        if os.path.exists(tpath) and default_shape and args.config == 1:
+            try:
+                raw = open(tpath, "rb").read()
+                traffic_sha = hashlib.sha1(raw).hexdigest()[:12]
+                tj = json.loads(raw)
+                traffic = tj.get(dom.split(" ")[0])
+                valu_insts = tj.get(dom.split(" ")[0] + "_valu_insts")
+                traffic_src_id = tj.get("kernel_source_id")
+            except Exception:
+                traffic = valu_insts = None
+        roofline = {
+            "bound": "hbm", "kernel": dom, "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK, "traffic": traffic,
+            "traffic_source": ("profiles/traffic.json sha1 %s (committed rocprofv3 --pmc passes of this workload; NOT measured in this run); "
+                               "counters taken on kernel sources %s, this build is %s: %s"
+                               % (traffic_sha, traffic_src_id, src_id, "MATCH" if traffic_src_id == src_id else "STALE counter file")
+                               if traffic else None),
+            "traffic_matches_build": (traffic_src_id == src_id) if traffic else None,
+            "kernel_source_id": src_id,
+            "traffic_frac": (traffic / avg_s / HBM_PEAK) if (traffic and avg_s > 0) else None,
+            "valu_floor_us": (valu_insts * 4.0 / (1024 * 2.4e9) * 1e6) if valu_insts else None,
+            "avg_launch_us": avg_s * 1e6, "timing_source": timing_source, "algorithmic_bytes_per_obs": bytes_per_obs,
+            "whole_iteration_frac": (run_bytes / elapsed) / (HBM_PEAK * world),
+            "whole_iteration_frac_nominal": (run_bytes_nominal / elapsed) / (HBM_PEAK * world),
+            "kernels_ms_per_launch": {k: (v[0] / max(1, v[1])) for k, v in kern.items()},
+            # the same figures for every timed kernel (the two big ones are within a few microseconds of each other)
+            "per_kernel": {k: {"avg_launch_us": 1e3 * v[0] / v[1], "algorithmic_bytes_per_obs": v[2],
+                               "frac": n_obs_local * v[2] / (1e-3 * v[0] / v[1]) / HBM_PEAK}
+                           for k, v in kern.items() if v[1] > 0 and v[0] > 0},
+        }
+        out.update({
+            "roofline": roofline,
+            "exchange": {"transport": eng.comm_transport(), "ranks_seen_by_transport": eng.comm_rank_count(),
+                         "us_per_step": (1e3 * ctr["exchange_ms"] / ctr["exchange_launches"]) if ctr["exchange_launches"] else 0.0,
+                         "note": "both per-step exchanges (packed reduced camera system + step scalars), HIP events on the engine's stream in the "
+                                 "profiled (host-stepped) solve; 0 at one rank"},
+            "pcie_inclusive": {"upload_ms": 1e3 * upload_s, "iters_per_sec": iters_done / (elapsed + upload_s),
+                               "note": "host->device upload of the whole window (frames, points, descriptors, observations, cameras) + the same solve"},
+            "device_copy_GBps": copy_gbps,
+        })
 
     def measure(eng_, prob_, steps, repeats, collective):
         """Median seconds per LM iteration of `repeats` timed solves of `steps` iterations on another engine / window
@@ -632,8 +704,8 @@ def main():
         e_.load(prob_)
         return e_
 
-    # ---- strong-scaling record of the SAME launch (N > 1, weak-scaling run): configs[3] by rank 0 alone, then sharded over the N ranks
-    if world > 1 and not strong and os.environ.get("PBA_BENCH_STRONG", "1") != "0":
+    # ---- strong-scaling record of the SAME launch (N > 1, weak-scaling run): configs[3] by rank 0 alone, then sharded over the N ranks (--full)
+    if args.full and world > 1 and not strong and os.environ.get("PBA_BENCH_STRONG", "1") != "0":
         try:
             n3 = int(os.environ.get("PBA_BENCH_STRONG_POINTS", "200000"))      # (tests shrink the window)
             whole3 = synthetic.make_window(n_frames=16, n_points=n3, radius=2, huber=0.0, dense_births=(0, 8))
@@ -707,8 +779,8 @@ def main():
                                              "scalar exchange kernel (host-stepped driver only)": per("exchange")},
         }
 
-    # ---- CPU baseline: the oracle ("restated Ceres-equivalent CPU path") on a bounded sample, rank 0, N = 1 ----
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_steps > 0 and not args.inverse_depth:
+    # ---- CPU baseline: the oracle ("restated Ceres-equivalent CPU path") on a bounded sample, rank 0, N = 1 (--full) ----
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_steps > 0 and not args.inverse_depth:
         from oracle import oracle
         n_cpu = min(args.cpu_points, prob.n_points, max(1000, int(400000 / n_bar / args.channels)))     # bounded: <= 400k single-channel residual blocks
         sub = prob.shard(0, 1)

@@ -94,7 +94,9 @@ __device__ __forceinline__ bool res_wait(unsigned* sync, int first, int n, unsig
     int vote = 0;
     for (int g = threadIdx.x; g < n; g += kResThreads) {
       const unsigned f = __hip_atomic_load(sync + (size_t)(first + g) * kResFlagStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if ((int)(f - ep) < 0) vote |= 1;
+      // (plain unsigned order: the epochs never wrap -- they restart below 0xF0000000 with the block zeroed -- whereas a
+      // wrap-around difference would take a zeroed flag for one ahead of any epoch past 2^31)
+      if (f < ep) vote |= 1;
     }
     if (threadIdx.x == kResThreads - 1 && (++spins & 63u) == 0) {
       if (__hip_atomic_load(sync + (size_t)kResFlagAbort * kResFlagStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) vote |= 2;

@@ -1,4 +1,4 @@
-"""bench.py contract on the GPU box: one JSON line with the agreed keys at N = 1, and the N = 2 launch path
+"""bench.py contract on the GPU box: one JSON line with the agreed keys at N = 1 (plain and --full), and the N = 2 launch path
 (torch.distributed.run, per-rank point shards, max-over-ranks timing, rank 0 prints).  Two ranks share the box's GPU
 through the PBA_BENCH_BACKEND=gloo hook: RCCL refuses duplicate devices, which also exercises the host-staged fallback
 transport bench.py switches to when RCCL cannot be initialised."""
@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +25,7 @@ def _json_line(out):
 @pytest.mark.timeout(900)
 def test_single_gpu_line():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--points", "20000",
-                        "--cpu-points", "2000", "--cpu-steps", "3"], capture_output=True, text=True, timeout=850, cwd=ROOT)
+                        "--full", "--cpu-points", "2000", "--cpu-steps", "3"], capture_output=True, text=True, timeout=850, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
     assert KEYS <= set(d) and d["n_gpus"] == 1 and d["steps"] == 10 and d["value"] > 0 and d["scaling"] == "weak"
@@ -40,11 +41,36 @@ def test_single_gpu_line():
 
 
 @pytest.mark.timeout(900)
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full): the headline keys, EXACTLY --steps timed LM iterations and none of the --full records; --dump-outputs
+    writes what the last timed solve returns as float64 arrays, bit for bit the same on a second run with the same arguments."""
+    outs = []
+    for k in range(2):
+        dump = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--frames", "4",
+                            "--points", "20000", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=400, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _json_line(r.stdout)
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(d) and d["higher_is_better"] is True
+        assert d["steps"] == 7 and d["repeats"] == 1 and d["lm"]["iterations"] == 7
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 1.0) < 1e-6
+        assert not {"roofline", "exchange", "pcie_inclusive", "device_copy_GBps", "cpu_baseline"} & set(d), sorted(d)
+        arrs = {n: np.load(dump / (n + ".npy")) for n in ("cams", "xyz", "iterations")}
+        assert all(a.dtype == np.float64 for a in arrs.values())
+        assert arrs["cams"].shape == (4, 6) and arrs["xyz"].shape == (20000, 3) and np.isfinite(arrs["xyz"]).all()
+        its = arrs["iterations"]
+        assert its.shape[0] >= 2 and np.array_equal(its[:, 0], np.arange(its.shape[0]))
+        outs.append(arrs)
+    for n in outs[0]:
+        assert np.array_equal(outs[0][n], outs[1][n]), n
+
+
+@pytest.mark.timeout(900)
 def test_two_rank_launch_path():
     env = dict(os.environ, PBA_BENCH_BACKEND="gloo", PBA_BENCH_STRONG_POINTS="6000")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8",
-                        "--warmup", "2", "--points", "10000"], capture_output=True, text=True, timeout=850, cwd=ROOT, env=env)
+                        "--warmup", "2", "--points", "10000", "--full"], capture_output=True, text=True, timeout=850, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
     assert d["n_gpus"] == 2 and d["steps"] == 8 and d["value"] > 0
@@ -65,7 +91,7 @@ def test_rank_of_eight_emulation_and_counter_file_id():
     """--config 3 --emulate-rank-of 8: the multi-rank code path at world = 1 on a shard, projected speed-up printed;
     and the roofline object says which build the committed counter file belongs to."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "3", "--emulate-rank-of", "8", "--points", "16000",
-                        "--steps", "6", "--warmup", "2", "--repeats", "3"], capture_output=True, text=True, timeout=850, cwd=ROOT)
+                        "--steps", "6", "--warmup", "2", "--repeats", "3", "--full"], capture_output=True, text=True, timeout=850, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
     sp = d["strong_projection"]

@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: tools/ab_bench.sh "<ENV=..>" [bench args]: prints ms/step and per-kernel shares
-env $1 python bench.py --no-cpu-baseline "${@:2}" 2>/dev/null | python -c '
+env $1 python bench.py --full --no-cpu-baseline "${@:2}" 2>/dev/null | python -c '
 import json, sys
 d = json.loads([l for l in sys.stdin if l.startswith("{")][0])
 r = d["roofline"]

@@ -9,7 +9,7 @@ for rep in $(seq 1 $N); do
   for spec in "$@"; do
     nm=${spec%%:*}; envs=""; [ "$spec" != "$nm" ] && envs=$(echo "${spec#*:}" | tr ',' ' ')
     lib=photobundle_amd/libpba_hip_$nm.so; [ "$nm" = main ] && lib=photobundle_amd/libpba_hip.so
-    env PBA_LIB=$lib $envs python bench.py --no-cpu-baseline $ARGS 2>/dev/null | python -c '
+    env PBA_LIB=$lib $envs python bench.py --full --no-cpu-baseline $ARGS 2>/dev/null | python -c '
 import json, sys
 d = json.loads([l for l in sys.stdin if l.startswith("{")][0])
 k = d["roofline"]["kernels_ms_per_launch"]

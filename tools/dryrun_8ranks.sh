@@ -7,7 +7,7 @@ set -u
 mkdir -p gpurun_out/dry8
 export PBA_BENCH_BACKEND=gloo
 export PBA_BENCH_STRONG_POINTS=${PBA_BENCH_STRONG_POINTS:-200000}
-timeout 1700 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29571 bench.py --gpus 8 --steps 20 --warmup 5 \
+timeout 1700 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29571 bench.py --gpus 8 --steps 20 --warmup 5 --full \
   > gpurun_out/dry8/dryrun_8ranks_1gpu.json 2> gpurun_out/dry8/dryrun_8ranks_1gpu.err
 echo "exit code $?" > gpurun_out/dry8/dryrun_8ranks_1gpu.txt
 python - <<'PY' >> gpurun_out/dry8/dryrun_8ranks_1gpu.txt 2>&1

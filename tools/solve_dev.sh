@@ -6,7 +6,7 @@ mkdir -p $OUT
 python -m pytest tests/test_gpu_parity.py tests/test_gpu_edge_cases.py tests/test_gpu_random_shapes.py tests/test_gpu_multirank.py tests/test_gpu_inverse_depth.py tests/test_gpu_multichannel.py -m gpu -x -q > $OUT/pytest.log 2>&1
 tail -15 $OUT/pytest.log
 for a in "--steps 20" "--steps 50" "--config 3 --steps 20 --repeats 5"; do
-  python bench.py --no-cpu-baseline $a 2>$OUT/bench.err | python -c '
+  python bench.py --full --no-cpu-baseline $a 2>$OUT/bench.err | python -c '
 import json, sys
 d = json.loads([l for l in sys.stdin if l.startswith("{")][0])
 r = d["roofline"]
