@@ -76,6 +76,12 @@ SYMBOLS = [
     "pba_frontend_visibility", "pba_frontend_candidates", "pba_frontend_get_candidates", "pba_frontend_descriptors", "pba_frontend_zncc_probe",
 ]
 
+# every symbol include/pba_stereo.h declares (the stereo matcher's own handle; photobundle_amd/stereo.py)
+STEREO_SYMBOLS = [
+    "pba_stereo_default_params", "pba_stereo_create", "pba_stereo_compute", "pba_stereo_last_error", "pba_stereo_destroy",
+    "pba_stereo_get_prefiltered", "pba_stereo_get_timing", "pba_stereo_validate_params",
+]
+
 
 def lib():
     """Returns the loaded CDLL; raises EngineUnavailable (never falls back) when the library is not built."""

@@ -1,22 +1,30 @@
 // run_kitti.cc -- the reference's driver loop (reference apps/run_kitti.cc:17-59) on the MI355X engine.
 //
-// OpenCV / the stereo matcher are outside the hot path and absent from this image, so frames come from a directory
-// of precomputed inputs instead of Dataset::Create:
-//     <data>/image_%06d.pgm   binary PGM (P5, 8 bit)
+// OpenCV is absent from this image, so frames come from a directory of PGM files instead of Dataset::Create:
+//     <data>/image_%06d.pgm   binary PGM (P5, 8 bit), the left image
 //     <data>/depth_%06d.bin   rows*cols float32 depth map (what disparityToDepth would hand over; <= 0 invalid)
-//     <data>/calib.txt        fx fy cx cy baseline
-// The config file is the reference's (config/kitti_stereo.cfg keys) plus `DataDirectory`; `Trajectory` is the KITTI
-// pose text file of frame-to-frame initial poses (reference data/kitti_init_poor/*.txt).
+//     <data>/right_%06d.pgm   the right image (DepthSource = stereo)
+//     <data>/calib.txt        fx fy cx cy baseline, or KITTI's own "P0: <12 numbers>" / "P1: <12 numbers>" lines
+//                             (K = P0[:, :3], baseline = -P1(0,3) / P1(0,0), reference src/dataset.cc:235-253)
+// The config file is the reference's (config/kitti_stereo.cfg keys) plus `DataDirectory` and `DepthSource`; `Trajectory` is
+// the KITTI pose text file of frame-to-frame initial poses (reference data/kitti_init_poor/*.txt).
+//     DepthSource = files    (default) depth from depth_%06d.bin
+//     DepthSource = stereo   depth from the left/right pair on the device: the config's StereoAlgorithm (BlockMatching) +
+//                            disparityToDepth with Bf = baseline * fx (reference apps/run_kitti.cc:29, src/dataset.cc:105-137)
+#include <algorithm>
+#include <cctype>
 #include <csignal>
 #include <cstdio>
 #include <fstream>
 #include <memory>
+#include <sstream>
 #include <string>
 #include <vector>
 
 #include "../host/photobundle.h"
 #include "../host/photobundle_pyramid.h"
 #include "../host/pose_utils.h"
+#include "../host/stereo_algorithm.h"
 #include "../host/utils.h"
 
 static volatile bool gStop = false;
@@ -36,6 +44,33 @@ static bool readPgm(const std::string& fn, std::vector<uint8_t>& img, int& rows,
   img.resize((size_t)rows * cols);
   ifs.read(reinterpret_cast<char*>(img.data()), img.size());
   return (bool)ifs;
+}
+
+// "fx fy cx cy baseline", or the KITTI calib.txt layout when the first token is a "P0:"-style label
+static Calibration loadCalibration(const std::string& fn) {
+  std::ifstream ifs(fn);
+  std::string first;
+  if (!(ifs >> first)) throw std::runtime_error("bad calib.txt");
+  Calibration calib;
+  if (first.back() == ':') {
+    double P[2][12];
+    for (int k = 0; k < 12; ++k)
+      if (!(ifs >> P[0][k])) throw std::runtime_error("bad calib.txt: " + first + " needs 12 numbers");
+    std::string second;
+    if (!(ifs >> second) || second.back() != ':') throw std::runtime_error("bad calib.txt: no second camera line");
+    for (int k = 0; k < 12; ++k)
+      if (!(ifs >> P[1][k])) throw std::runtime_error("bad calib.txt: " + second + " needs 12 numbers");
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) calib.K()(r, c) = P[0][r * 4 + c];
+    calib.baseline() = -P[1][3] / P[1][0];
+    return calib;
+  }
+  double c5[5];
+  std::istringstream first_ss(first);
+  if (!(first_ss >> c5[0]) || !(ifs >> c5[1] >> c5[2] >> c5[3] >> c5[4])) throw std::runtime_error("bad calib.txt");
+  calib.setParameters(c5);
+  calib.baseline() = c5[4];
+  return calib;
 }
 
 static void dumpResult(const std::string& fn, int frame, const PhotometricBundleAdjustment::Result& r) {
@@ -76,22 +111,21 @@ int main(int argc, char** argv) {
   try {
     utils::ConfigFile cf(config);
     const std::string data = cf.get<std::string>("DataDirectory");
-    double c5[5];
-    {
-      std::ifstream ifs(data + "/calib.txt");
-      if (!(ifs >> c5[0] >> c5[1] >> c5[2] >> c5[3] >> c5[4])) throw std::runtime_error("bad calib.txt");
-    }
-    Calibration calib;
-    calib.setParameters(c5);
-    calib.baseline() = c5[4];
+    const Calibration calib = loadCalibration(data + "/calib.txt");
+    std::string depth_source = cf.get<std::string>("DepthSource", "files");
+    std::transform(depth_source.begin(), depth_source.end(), depth_source.begin(), [](unsigned char c) { return std::tolower(c); });
+    if (depth_source != "files" && depth_source != "stereo") throw std::runtime_error("DepthSource must be files or stereo, not " + depth_source);
     const auto T_init = loadPosesKittiFormat(cf.get<std::string>("trajectory"));
 
-    std::vector<uint8_t> img;
+    std::vector<uint8_t> img, right;
     std::vector<float> depth;
     int rows = 0, cols = 0;
     char name[64];
     std::snprintf(name, sizeof(name), "/image_%06d.pgm", 0);
     if (!readPgm(data + name, img, rows, cols)) throw std::runtime_error("cannot read the first frame");
+    std::unique_ptr<StereoAlgorithm> stereo;
+    const float Bf = (float)(calib.b() * calib.fx());
+    if (depth_source == "stereo") stereo.reset(new StereoAlgorithm(cf));
 
     PhotometricBundleAdjustment::Result result;
     const int num_levels = cf.get<int>("numLevels", 1);   // > 1: coarse-to-fine (photobundle_pyramid path)
@@ -104,10 +138,17 @@ int main(int argc, char** argv) {
       int r2, c2;
       if (!readPgm(data + name, img, r2, c2)) break;
       if (r2 != rows || c2 != cols) throw std::runtime_error("frame size changed");
-      std::snprintf(name, sizeof(name), "/depth_%06d.bin", f_i);
       depth.resize((size_t)rows * cols);
-      std::ifstream dfs(data + name, std::ios::binary);
-      if (!dfs.read(reinterpret_cast<char*>(depth.data()), depth.size() * sizeof(float))) throw std::runtime_error("bad depth file");
+      if (stereo) {
+        std::snprintf(name, sizeof(name), "/right_%06d.pgm", f_i);
+        if (!readPgm(data + name, right, r2, c2)) throw std::runtime_error(std::string("cannot read ") + (name + 1));
+        if (r2 != rows || c2 != cols) throw std::runtime_error("right frame size differs");
+        stereo->depth(img.data(), right.data(), ImageSize(rows, cols), Bf, depth.data());
+      } else {
+        std::snprintf(name, sizeof(name), "/depth_%06d.bin", f_i);
+        std::ifstream dfs(data + name, std::ios::binary);
+        if (!dfs.read(reinterpret_cast<char*>(depth.data()), depth.size() * sizeof(float))) throw std::runtime_error("bad depth file");
+      }
       std::printf("Frame %05d\n", f_i);
       result.initialCost = -1.0;    // the class only touches `result` when an optimisation ran (photobundle.cc:857)
       if (photoba_pyr) photoba_pyr->addFrame(img.data(), depth.data(), T_init[f_i], &result);

@@ -141,4 +141,18 @@ inline void computeBitPlanes(const uint8_t* image, int rows, int cols, std::vect
 
 }  // namespace imgproc
 
+// disparity -> depth (reference src/imgproc.cc:280-322, same signature, global scope as there): Bf / d where d > 0.01, else -0.1.
+// Two correctly rounded fp32 operations, Bf * (1 / d), in every pixel: the reference's SSE body multiplies by _mm_rcp_ps (a
+// ~12-bit approximation) and its scalar tail marks invalid pixels with -1; the exact form is the one the device matcher's fused
+// epilogue (include/pba_stereo.h) restates, so StereoAlgorithm::run followed by this equals StereoAlgorithm::depth byte for byte.
+inline void disparityToDepth(const float* dmap, const ImageSize& im_size, float Bf, float* zmap) {
+  constexpr float MinValidDisparity = 0.01f;
+  constexpr float InvalidDepthMark = -0.1f;
+  const int n = im_size.numel();
+  for (int i = 0; i < n; ++i) {
+    const float d = dmap[i];
+    zmap[i] = d > MinValidDisparity ? Bf * (1.0f / d) : InvalidDepthMark;
+  }
+}
+
 #endif
