@@ -125,7 +125,9 @@ typedef struct pba_solver_summary {
   double total_time_in_seconds;
   int64_t num_jacobian_passes;       /* linearisations (residual + Jacobian) */
   int64_t num_cost_passes;           /* candidate (residual-only) evaluations */
-  int64_t num_resolve_passes;        /* extra damped Schur solves after rejected / invalid steps */
+  int64_t num_resolve_passes;        /* extra damped Schur solves after rejected / invalid steps.  Driver-dependent: the device
+                                      * drivers report num_unsuccessful_steps; the host-stepped driver counts the re-solves it
+                                      * actually ran.  The two can differ by one where the solve ends */
   char message[256];
 } pba_solver_summary;
 
