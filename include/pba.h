@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PBA_MAX_FRAMES 16
+#define PBA_MAX_FRAMES 32
 #define PBA_MAX_RADIUS 5
 #define PBA_MAX_CHANNELS 8
 
@@ -53,7 +53,7 @@ typedef enum pba_status {
  * slidingWindowSize / robustThreshold (photobundle.h:26-85). */
 typedef struct pba_config {
   int32_t rows, cols;        /* image size */
-  int32_t max_frames;        /* window slots (Options::slidingWindowSize), <= PBA_MAX_FRAMES */
+  int32_t max_frames;        /* window slots (Options::slidingWindowSize), 2..PBA_MAX_FRAMES (32) */
   int32_t radius;            /* Options::patchRadius, 1..PBA_MAX_RADIUS */
   double fx, fy, cx, cy;     /* pinhole intrinsics */
   double huber;              /* Options::robustThreshold; <= 0 disables the loss (photobundle.cc:797-798) */
@@ -243,8 +243,10 @@ int pba_frontend_zncc_probe(pba_engine* e, int32_t n, const double* uv, const fl
  * Call order: pba_set_frame_u8 (every slot the observation list uses), pba_set_problem and pba_set_cameras may come in
  * any order, all three before pba_linearize / pba_solve; a pass that finds one of them missing, an observation whose
  * slot is >= n_frames, or a slot without an uploaded frame returns PBA_ERR_STATE (nothing is launched).
- * Limit: at most 15 FREE cameras (n_frames - 1 with a constant camera, i.e. 16 window slots need fixed_slot >= 0);
- * pba_set_cameras returns PBA_ERR_INVALID beyond that. */
+ * Limit: at most 32 FREE cameras (n_frames <= max_frames <= PBA_MAX_FRAMES).  The window shape picks the path at
+ * pba_set_cameras: up to 15 free cameras the narrow kernels and drivers, 16 to 32 the wide chain (host-stepped driver).
+ * A wide window refuses the multi-rank transports (pba_comm_*), the inverse-depth mode and the precision-sweep flags:
+ * PBA_ERR_INVALID with a message in pba_last_error, whichever of the calls comes second. */
 int pba_set_problem(pba_engine* e, int32_t n_points, const double* xyz, const double* desc,
                     int32_t n_obs, const int32_t* obs_point, const int32_t* obs_slot, const double* weights);
 /* cams6: [n_frames][6]; fixed_slot: SetParameterBlockConstant (photobundle.cc:809-813), -1 for none. */

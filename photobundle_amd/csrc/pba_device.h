@@ -7,7 +7,8 @@
 
 namespace pba {
 
-constexpr int kMaxFrames = 16;
+constexpr int kMaxFrames = 16;        // camera tables of the narrow kernels (windows of <= 15 free cameras)
+constexpr int kMaxFramesWide = 32;    // PBA_MAX_FRAMES: camera tables of the wide-window chain (pba_wide.h)
 constexpr int kMaxRadius = 5;
 
 // Packed frame texel (one u32 per pixel), bit-exact for u8 frames:

@@ -9,6 +9,7 @@
 #include "pba_kernels.h"
 #include "pba_frontend.h"
 #include "pba_resident.h"
+#include "pba_wide.h"
 
 #include <algorithm>
 #include <chrono>
@@ -83,8 +84,8 @@ struct pba_engine {
   double* d_rec[2] = {nullptr, nullptr};   // [6][rec_stride] per point parity
   double* d_sp = nullptr;           // [n_points][3]
   double* d_ptrec = nullptr;        // [n_points][12]
-  double* d_sc = nullptr;           // [2][6 * kMaxFrames]: Jacobi scales | live flags (the [1] part starts at 6 n_free)
-  double* d_delta_c = nullptr;      // [kMaxFrames][6]
+  double* d_sc = nullptr;           // [2][6 * max(kMaxFrames, max_frames)]: Jacobi scales | live flags (the [1] part starts at 6 n_free)
+  double* d_delta_c = nullptr;      // [max(kMaxFrames, max_frames)][6]
   double* d_partial = nullptr;      // [schur_grid][part_stride]
   double* d_red = nullptr;          // [kChunks][part_stride]
   double* d_packed = nullptr;       // [part_stride] (the tri layout of pba_solve.h needs packed_stride(n) < part_stride of them)
@@ -140,6 +141,18 @@ struct pba_engine {
   int dbg_left = 0;
   int n_pairs = 0, part_stride = 0;
   static constexpr int kChunks = 32;
+  // wide windows (kWideMinFree..kMaxFramesWide free cameras, pba_wide.h): chosen by pba_set_cameras from the window shape
+  bool wide = false;
+  bool wide_ready = false;          // the co-observation lists below match the current problem and camera set
+  std::vector<int32_t> h_pt_begin;  // host copies of the observation structure
+  std::vector<uint8_t> h_obs_slot;
+  double* d_wfac = nullptr;         // [n_obs][kWideFac] observation factors
+  double* d_wpt_part = nullptr;     // [point blocks][3]
+  int2* d_went = nullptr;           // co-observations, pair-major
+  int4* d_wchunk = nullptr;         // [wide_chunks] {first entry, end, diagonal, pair}
+  int32_t* d_wpair_chunk = nullptr; // [n_pairs + 1]
+  double* d_wsums = nullptr;        // [wide_chunks][kWideVals]
+  int wide_chunks = 0, wide_pt_blocks = 0;
 
   Comm comm;
   unsigned int* h_comm_err = nullptr;      // host-mapped: a peer-exchange wait timed out (k_peer_allreduce)
@@ -212,7 +225,7 @@ int check_ready(pba_engine* e, const char* who) {
   if (e->poisoned) return fail(e, PBA_ERR_STATE, "%s: the engine is unusable after a timed-out step (stalled stream / collective); destroy it", who);
   if (!e->have_problem || !e->have_cams)
     return fail(e, PBA_ERR_STATE, "call order violated: %s before set_problem/set_cameras", who);
-  for (int s = 0; s < kMaxFrames; ++s) {
+  for (int s = 0; s < kMaxFramesWide; ++s) {
     if (!((e->slot_mask >> s) & 1u)) continue;
     if (s >= e->n_frames) return fail(e, PBA_ERR_STATE, "call order violated: an observation uses slot %d but only %d cameras are set", s, e->n_frames);
     if (!e->frame_set[s]) return fail(e, PBA_ERR_STATE, "call order violated: an observation uses slot %d but no frame was uploaded to it", s);
@@ -222,7 +235,9 @@ int check_ready(pba_engine* e, const char* who) {
 
 constexpr int kSampleWaves = 4;    // 256-thread workgroups at every patch radius (two 128-observation tiles when fused)
 
-template <int R, bool JAC, bool FUSED>
+// MF: camera-table length of the sampling kernels -- kMaxFrames, or kMaxFramesWide on wide windows (unfused, exact precision only:
+// pba_set_cameras refuses the sweep modes there)
+template <int R, bool JAC, bool FUSED, int MF>
 void launch_sample_r(pba_engine* e, const SampleParams& sp) {
   const int grid = FUSED ? e->fused_grid : e->sample_grid;
   const dim3 block(kSampleWaves * 64);
@@ -230,41 +245,52 @@ void launch_sample_r(pba_engine* e, const SampleParams& sp) {
     // the reduced-precision sweep modes never take the fused path (fused_capable)
     if (e->unit_weights) hipLaunchKernelGGL((k_sample<R, JAC, kSampleWaves, true, true, false>), dim3(grid), block, 0, e->stream, sp);
     else hipLaunchKernelGGL((k_sample<R, JAC, kSampleWaves, true, false, false>), dim3(grid), block, 0, e->stream, sp);
+  } else if constexpr (MF != kMaxFrames) {
+    if (e->unit_weights) hipLaunchKernelGGL((k_sample<R, JAC, kSampleWaves, false, true, false, MF>), dim3(grid), block, 0, e->stream, sp);
+    else hipLaunchKernelGGL((k_sample<R, JAC, kSampleWaves, false, false, false, MF>), dim3(grid), block, 0, e->stream, sp);
   } else {
     if (e->unit_weights && sp.prec != 0) hipLaunchKernelGGL((k_sample<R, JAC, kSampleWaves, false, true, true>), dim3(grid), block, 0, e->stream, sp);
     else if (e->unit_weights) hipLaunchKernelGGL((k_sample<R, JAC, kSampleWaves, false, true, false>), dim3(grid), block, 0, e->stream, sp);
     else hipLaunchKernelGGL((k_sample<R, JAC, kSampleWaves, false, false, false>), dim3(grid), block, 0, e->stream, sp);
   }
 }
-template <int R, bool JAC, bool FUSED>
+template <int R, bool JAC, bool FUSED, int MF>
 void launch_sample_mc_r(pba_engine* e, const SampleParams& sp) {
   const dim3 grid(FUSED ? e->fused_grid : e->sample_grid), block(kSampleWaves * 64);
-  if (e->unit_weights) hipLaunchKernelGGL((k_sample_mc<R, JAC, kSampleWaves, FUSED, true>), grid, block, 0, e->stream, sp, (const float*)e->d_frames_mc, e->channels);
-  else hipLaunchKernelGGL((k_sample_mc<R, JAC, kSampleWaves, FUSED, false>), grid, block, 0, e->stream, sp, (const float*)e->d_frames_mc, e->channels);
+  if (e->unit_weights) hipLaunchKernelGGL((k_sample_mc<R, JAC, kSampleWaves, FUSED, true, MF>), grid, block, 0, e->stream, sp, (const float*)e->d_frames_mc, e->channels);
+  else hipLaunchKernelGGL((k_sample_mc<R, JAC, kSampleWaves, FUSED, false, MF>), grid, block, 0, e->stream, sp, (const float*)e->d_frames_mc, e->channels);
 }
-template <bool JAC, bool FUSED = false>
-void launch_sample(pba_engine* e, const SampleParams& sp) {
+template <bool JAC, bool FUSED, int MF>
+void launch_sample_mf(pba_engine* e, const SampleParams& sp) {
   if (e->channels > 1) {
     switch (e->cfg.radius) {
-      case 1: launch_sample_mc_r<1, JAC, FUSED>(e, sp); break;
-      case 2: launch_sample_mc_r<2, JAC, FUSED>(e, sp); break;
-      case 3: launch_sample_mc_r<3, JAC, FUSED>(e, sp); break;
-      case 4: launch_sample_mc_r<4, JAC, FUSED>(e, sp); break;
-      default: launch_sample_mc_r<5, JAC, FUSED>(e, sp); break;
+      case 1: launch_sample_mc_r<1, JAC, FUSED, MF>(e, sp); break;
+      case 2: launch_sample_mc_r<2, JAC, FUSED, MF>(e, sp); break;
+      case 3: launch_sample_mc_r<3, JAC, FUSED, MF>(e, sp); break;
+      case 4: launch_sample_mc_r<4, JAC, FUSED, MF>(e, sp); break;
+      default: launch_sample_mc_r<5, JAC, FUSED, MF>(e, sp); break;
     }
     return;
   }
   switch (e->cfg.radius) {
-    case 1: launch_sample_r<1, JAC, FUSED>(e, sp); break;
-    case 2: launch_sample_r<2, JAC, FUSED>(e, sp); break;
-    case 3: launch_sample_r<3, JAC, FUSED>(e, sp); break;
-    case 4: launch_sample_r<4, JAC, FUSED>(e, sp); break;
-    default: launch_sample_r<5, JAC, FUSED>(e, sp); break;
+    case 1: launch_sample_r<1, JAC, FUSED, MF>(e, sp); break;
+    case 2: launch_sample_r<2, JAC, FUSED, MF>(e, sp); break;
+    case 3: launch_sample_r<3, JAC, FUSED, MF>(e, sp); break;
+    case 4: launch_sample_r<4, JAC, FUSED, MF>(e, sp); break;
+    default: launch_sample_r<5, JAC, FUSED, MF>(e, sp); break;
   }
+}
+template <bool JAC, bool FUSED = false>
+void launch_sample(pba_engine* e, const SampleParams& sp) {
+  if constexpr (!FUSED) {
+    if (e->wide) { launch_sample_mf<JAC, false, kMaxFramesWide>(e, sp); return; }
+  }
+  launch_sample_mf<JAC, FUSED, kMaxFrames>(e, sp);
 }
 // one kernel for back-substitution + candidate pass + step finalisation, at every patch radius; the opt-in
 // reduced-precision sampler modes (pba_config.flags bits 1-2) keep the unfused kernels
-bool fused_capable(const pba_engine* e) { return e->fuse && ((e->cfg.flags >> 1) & 3) == 0; }
+// (wide windows run the unfused chain: the fused kernels stage kMaxFrames-entry tables)
+bool fused_capable(const pba_engine* e) { return e->fuse && ((e->cfg.flags >> 1) & 3) == 0 && !e->wide; }
 int sample_waves_for_radius(int) { return kSampleWaves; }
 
 __global__ void k_noop() {}
@@ -410,6 +436,100 @@ void launch_schur(pba_engine* e, const SchurParams& sp) {
   hipLaunchKernelGGL(k_schur, dim3(e->schur_grid), dim3(kTile), 0, e->stream, sp);
 }
 
+// ---- wide windows (pba_wide.h) ------------------------------------------------------------------------------------
+// Co-observation lists, built on the host once per problem and camera set: for every pair of free cameras a <= b (enumerated
+// row by row, as the packed pair blocks) the (observation of a, observation of b) of every point both observe, in point order,
+// cut into chunks of kWideChunk.  A causal window is banded: pairs of cameras far apart share few points or none.
+int wide_prepare(pba_engine* e) {
+  if (e->wide_ready) return PBA_OK;
+  const int nf = e->n_free, fixed = e->fixed_slot, n_pairs = e->n_pairs;
+  auto free_of = [&](int s) { return s == fixed ? -1 : (fixed >= 0 && s > fixed ? s - 1 : s); };
+  auto pair_of = [&](int a, int b) { return a * nf - a * (a - 1) / 2 + (b - a); };
+  std::vector<int64_t> off((size_t)n_pairs + 1, 0);
+  int fa[kMaxFramesWide], lo[kMaxFramesWide];
+  auto point_obs = [&](int p) {     // free-camera observations of point p (slots ascending, so free indices ascending)
+    int k = 0;
+    for (int o = e->h_pt_begin[p]; o < e->h_pt_begin[p + 1]; ++o) {
+      const int f = free_of(e->h_obs_slot[o]);
+      if (f >= 0) { fa[k] = f; lo[k] = o; ++k; }
+    }
+    return k;
+  };
+  for (int p = 0; p < e->n_points; ++p) {
+    const int k = point_obs(p);
+    for (int i = 0; i < k; ++i)
+      for (int j = i; j < k; ++j) off[(size_t)pair_of(fa[i], fa[j]) + 1]++;
+  }
+  for (int q = 0; q < n_pairs; ++q) off[q + 1] += off[q];
+  const int64_t n_ent = off[n_pairs];
+  if (n_ent >= (1ll << 31) - kWideChunk)
+    return fail(e, PBA_ERR_INVALID, "wide window: %lld co-observations exceed the int32 range of the pair lists", (long long)n_ent);
+  std::vector<int2> ent((size_t)std::max<int64_t>(n_ent, 1));
+  {
+    std::vector<int64_t> fill(off.begin(), off.end() - 1);
+    for (int p = 0; p < e->n_points; ++p) {
+      const int k = point_obs(p);
+      for (int i = 0; i < k; ++i)
+        for (int j = i; j < k; ++j) ent[(size_t)fill[pair_of(fa[i], fa[j])]++] = make_int2(lo[i], lo[j]);
+    }
+  }
+  std::vector<int4> chunks;
+  std::vector<int32_t> pair_chunk((size_t)n_pairs + 1, 0);
+  for (int q = 0, a = 0, b = 0; q < n_pairs; ++q) {
+    pair_chunk[q] = (int32_t)chunks.size();
+    for (int64_t c = off[q]; c < off[q + 1]; c += kWideChunk)
+      chunks.push_back(make_int4((int)c, (int)std::min<int64_t>(c + kWideChunk, off[q + 1]), a == b ? 1 : 0, q));
+    if (++b == nf) { ++a; b = a; }
+  }
+  pair_chunk[n_pairs] = (int32_t)chunks.size();
+  e->wide_chunks = (int)chunks.size();
+  e->wide_pt_blocks = (e->n_points + kWideThreads - 1) / kWideThreads;
+  int rc;
+  if ((rc = dev_alloc(e, &e->d_went, ent.size()))) return rc;
+  if ((rc = dev_alloc(e, &e->d_wchunk, std::max<size_t>(chunks.size(), 1)))) return rc;
+  if ((rc = dev_alloc(e, &e->d_wpair_chunk, pair_chunk.size()))) return rc;
+  if ((rc = dev_alloc(e, &e->d_wsums, std::max<size_t>(chunks.size(), 1) * kWideVals))) return rc;
+  if ((rc = dev_alloc(e, &e->d_wfac, (size_t)e->n_obs * kWideFac))) return rc;
+  if ((rc = dev_alloc(e, &e->d_wpt_part, (size_t)3 * e->wide_pt_blocks))) return rc;
+  HIP_TRY(e, hipMemcpyAsync(e->d_went, ent.data(), sizeof(int2) * ent.size(), hipMemcpyHostToDevice, e->stream));
+  if (!chunks.empty()) HIP_TRY(e, hipMemcpyAsync(e->d_wchunk, chunks.data(), sizeof(int4) * chunks.size(), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(e->d_wpair_chunk, pair_chunk.data(), sizeof(int32_t) * pair_chunk.size(), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));      // (the host vectors go out of scope)
+  e->wide_ready = true;
+  return PBA_OK;
+}
+
+// Schur elimination of a wide window: point stage, pair stage, assembly into the packed reduced system (profiling: the Schur share)
+int wide_eliminate(pba_engine* e, int cur, int init_scale, const pba_solver_options* o, double radius) {
+  { const int rc = wide_prepare(e); if (rc) return rc; }
+  WidePointParams wp{};
+  wp.xyz = e->d_xyz[cur]; wp.geom = e->d_geom[cur]; wp.rec = e->d_rec[cur]; wp.pt_begin = e->d_pt_begin; wp.obs_slot = e->d_obs_slot;
+  wp.sp = e->d_sp; wp.ptrec = e->d_ptrec; wp.fac = e->d_wfac; wp.part = e->d_wpt_part; wp.rec_stride = e->rec_stride;
+  wp.n_points = e->n_points; wp.n_frames = e->n_frames; wp.init_scale = init_scale; wp.jacobi = o->jacobi_scaling;
+  wp.fx = e->cfg.fx; wp.fy = e->cfg.fy; wp.inv_radius = 1.0 / radius; wp.min_diag = o->min_lm_diagonal; wp.max_diag = o->max_lm_diagonal;
+  WidePairParams pp{};
+  pp.fac = e->d_wfac; pp.ent = e->d_went; pp.chunk = e->d_wchunk; pp.out = e->d_wsums;
+  WideAssembleParams ap{};
+  ap.chunk_sums = e->d_wsums; ap.pair_chunk = e->d_wpair_chunk; ap.pt_part = e->d_wpt_part; ap.n_pt_blocks = e->wide_pt_blocks;
+  ap.block_cost = e->d_block_cost[cur]; ap.block_fail = e->d_block_fail[cur]; ap.n_cost_blocks = e->cost_blocks[cur];
+  ap.packed = e->d_packed; ap.scal = e->d_scal; ap.n_free = e->n_free; ap.n_pairs = e->n_pairs;
+  ev_begin(e, 2);
+  hipLaunchKernelGGL(k_wide_point, dim3(e->wide_pt_blocks), dim3(kWideThreads), 0, e->stream, wp);
+  if (e->wide_chunks > 0) hipLaunchKernelGGL(k_wide_pairs, dim3(e->wide_chunks), dim3(kWideThreads), 0, e->stream, pp);
+  hipLaunchKernelGGL(k_wide_assemble, dim3(e->n_pairs + 1), dim3(128), 0, e->stream, ap);
+  ev_end(e, 2);
+  HIP_TRY(e, hipGetLastError());
+  return PBA_OK;
+}
+
+// Why a wide window cannot run with what the engine has been given (nullptr: it can)
+const char* wide_refusal(const pba_engine* e) {
+  if (e->comm.multi()) return "multi-rank solves (pba_comm_*) are not built for wide windows";
+  if (e->inverse_depth) return "the inverse-depth mode (pba_set_inverse_depth) is not built for wide windows";
+  if ((e->cfg.flags >> 1) & 3) return "the precision-sweep sampler modes (pba_config.flags bits 1-2) are not built for wide windows";
+  return nullptr;
+}
+
 SampleParams make_sample_params(pba_engine* e, int which_point) {
   const int which_out = which_point;
   SampleParams sp{};
@@ -511,7 +631,7 @@ static int ensure_state_stage(pba_engine* e, size_t doubles) {
 int pba_create(const pba_config* cfg, pba_engine** out) {
   if (!cfg || !out) return PBA_ERR_INVALID;
   *out = nullptr;
-  if (cfg->rows < 8 || cfg->cols < 8 || cfg->max_frames < 2 || cfg->max_frames > kMaxFrames || cfg->radius < 1 ||
+  if (cfg->rows < 8 || cfg->cols < 8 || cfg->max_frames < 2 || cfg->max_frames > kMaxFramesWide || cfg->radius < 1 ||
       cfg->radius > kMaxRadius || (int64_t)cfg->rows * cfg->cols * cfg->max_frames >= (1ll << 31))
     return PBA_ERR_INVALID;
   if (cfg->channels < 0 || cfg->channels > PBA_MAX_CHANNELS ||
@@ -542,15 +662,17 @@ int pba_create(const pba_config* cfg, pba_engine** out) {
     if (hipMemsetAsync(e->d_frames_mc, 0, npix * cfg->max_frames * e->channels * sizeof(float), e->stream) != hipSuccess) return bail(PBA_ERR_HIP);
   }
   e->frame_set.assign(cfg->max_frames, 0);
+  // per-camera buffers: kMaxFrames slots as ever, more for an engine that may see a wide window
+  const int mf = std::max(kMaxFrames, cfg->max_frames);
   for (int k = 0; k < 2; ++k) {
-    if ((rc = dev_alloc(e, &e->d_cams[k], 6 * kMaxFrames))) return bail(rc);
-    if ((rc = dev_alloc(e, &e->d_geom[k], kMaxFrames))) return bail(rc);
+    if ((rc = dev_alloc(e, &e->d_cams[k], 6 * mf))) return bail(rc);
+    if ((rc = dev_alloc(e, &e->d_geom[k], mf))) return bail(rc);
   }
-  if ((rc = dev_alloc(e, &e->d_sc, 2 * 6 * kMaxFrames))) return bail(rc);
-  if ((rc = dev_alloc(e, &e->d_delta_c, 6 * kMaxFrames))) return bail(rc);
+  if ((rc = dev_alloc(e, &e->d_sc, 2 * 6 * mf))) return bail(rc);
+  if ((rc = dev_alloc(e, &e->d_delta_c, 6 * mf))) return bail(rc);
   if ((rc = dev_alloc(e, &e->d_scal, (size_t)kNumScal))) return bail(rc);
-  if ((rc = dev_alloc(e, &e->d_S, (size_t)36 * kMaxFrames * kMaxFrames))) return bail(rc);
-  if ((rc = dev_alloc(e, &e->d_rhs, (size_t)6 * kMaxFrames))) return bail(rc);
+  if ((rc = dev_alloc(e, &e->d_S, (size_t)36 * mf * mf))) return bail(rc);
+  if ((rc = dev_alloc(e, &e->d_rhs, (size_t)6 * mf))) return bail(rc);
   if (hipMemsetAsync(e->d_scal, 0, kNumScal * sizeof(double), e->stream) != hipSuccess) return bail(PBA_ERR_HIP);
   if (hipHostMalloc(reinterpret_cast<void**>(&e->h_scal), (kNumScal + 1) * sizeof(double), hipHostMallocMapped) != hipSuccess) return bail(PBA_ERR_HIP);
   std::memset(e->h_scal, 0, (kNumScal + 1) * sizeof(double));
@@ -588,7 +710,7 @@ int pba_create(const pba_config* cfg, pba_engine** out) {
     if (hipEventCreate(&e->ev[k]) != hipSuccess) return bail(PBA_ERR_HIP);
   if (hipEventCreateWithFlags(&e->ev_xdep, hipEventDisableTiming) != hipSuccess) return bail(PBA_ERR_HIP);
   e->sample_waves = sample_waves_for_radius(cfg->radius);
-  if ((rc = ensure_state_stage(e, (size_t)6 * kMaxFrames + 3 * 65536))) return bail(rc);   // grown on demand beyond 64k points
+  if ((rc = ensure_state_stage(e, (size_t)6 * mf + 3 * 65536))) return bail(rc);   // grown on demand beyond 64k points
   // The first frame-sized host -> device DMA of a process costs ~8 ms (seen in the drop-in class: first
   // pba_set_frame_u8): paid here, from the engine's own pinned buffer
   if (hipMemcpyAsync(e->d_img_stage, e->h_img_stage, npix, hipMemcpyHostToDevice, e->stream) != hipSuccess) return bail(PBA_ERR_HIP);
@@ -638,6 +760,7 @@ void pba_destroy(pba_engine* e) {
   dev_free(&e->d_lm);
   dev_free(&e->d_log);
   dev_free(&e->d_res_sync);
+  dev_free(&e->d_wfac); dev_free(&e->d_wpt_part); dev_free(&e->d_went); dev_free(&e->d_wchunk); dev_free(&e->d_wpair_chunk); dev_free(&e->d_wsums);
   for (int k = 0; k < 2 * pba_engine::kEvPairs; ++k) if (e->ev[k]) (void)hipEventDestroy(e->ev[k]);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
@@ -1099,6 +1222,9 @@ int pba_set_problem(pba_engine* e, int32_t n_points, const double* xyz, const do
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   e->slot_mask = 0;
   for (int o = 0; o < n_obs; ++o) e->slot_mask |= 1u << slot8[o];
+  e->h_pt_begin = std::move(pt_begin);      // (wide_prepare; moved, not copied)
+  e->h_obs_slot = std::move(slot8);
+  e->wide_ready = false;
   e->have_problem = true;
   e->inverse_depth = false;         // back to the reference's free world points until pba_set_inverse_depth says otherwise
   e->have_lin = false;
@@ -1110,13 +1236,32 @@ int pba_set_cameras(pba_engine* e, const double* cams6, int32_t n_frames, int32_
   if (!e || !cams6 || n_frames < 2 || n_frames > e->cfg.max_frames || fixed_slot >= n_frames) return PBA_ERR_INVALID;
   PBA_NOT_POISONED(e);
   HIP_TRY(e, hipSetDevice(e->cfg.device));
+  {
+    // the window shape picks the path: up to kWideMinFree - 1 free cameras the narrow kernels, beyond them the wide chain
+    const int nf = n_frames - (fixed_slot >= 0 ? 1 : 0);
+    const char* why = nf >= kWideMinFree ? wide_refusal(e) : nullptr;
+    if (why) return fail(e, PBA_ERR_INVALID, "pba_set_cameras: %d free cameras: %s (at most %d free cameras there)", nf, why, kWideMinFree - 1);
+    if (nf >= kWideMinFree) {
+      int lds_max = 0;
+      const size_t need = solve_wide_smem_bytes(6 * nf) + 1024;
+      if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, e->cfg.device) == hipSuccess && lds_max > 0 && need > (size_t)lds_max)
+        return fail(e, PBA_ERR_INVALID, "%d free cameras need %zu bytes of LDS for the reduced solve, the device offers %d per workgroup", nf, need, lds_max);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_wide), hipFuncAttributeMaxDynamicSharedMemorySize, (int)solve_wide_smem_bytes(6 * nf));
+      (void)hipGetLastError();
+    }
+  }
   e->n_frames = n_frames;
   e->fixed_slot = fixed_slot < 0 ? -1 : fixed_slot;
   e->n_free = n_frames - (e->fixed_slot >= 0 ? 1 : 0);
   e->n_pairs = e->n_free * (e->n_free + 1) / 2;
   e->part_stride = 36 * e->n_pairs + 3 * 6 * e->n_free + 3;
-  if (e->n_pairs > kTile) return fail(e, PBA_ERR_INVALID, "too many free cameras for the Schur tile (%d pairs)", e->n_pairs);
-  {
+  e->wide = e->n_free >= kWideMinFree;
+  e->wide_ready = false;
+  int rc;
+  if (e->wide) {
+    if ((rc = dev_alloc(e, &e->d_packed, (size_t)packed_stride(6 * e->n_free)))) return rc;
+  } else {
+    if (e->n_pairs > kTile) return fail(e, PBA_ERR_INVALID, "too many free cameras for the Schur tile (%d pairs)", e->n_pairs);
     // the reduced solve keeps the whole augmented matrix in LDS (dynamic) next to ~21 KB of static LDS: fits the 160 KB of a
     // gfx950 CU at every supported window; a device with less (gfx90a / gfx942: 64 KB) gets a clear error instead of a failed launch
     int lds_max = 0;
@@ -1125,11 +1270,10 @@ int pba_set_cameras(pba_engine* e, const double* cams6, int32_t n_frames, int32_
       if (need > (size_t)lds_max)
         return fail(e, PBA_ERR_INVALID, "%d free cameras need %zu bytes of LDS for the reduced solve, the device offers %d per workgroup", e->n_free, need, lds_max);
     }
+    if ((rc = dev_alloc(e, &e->d_partial, (size_t)(256 * 4) * (((size_t)e->part_stride + 15) / 16 * 16)))) return rc;      // [entry / 16][workgroup][16]
+    if ((rc = dev_alloc(e, &e->d_red, (size_t)pba_engine::kChunks * e->part_stride))) return rc;
+    if ((rc = dev_alloc(e, &e->d_packed, (size_t)e->part_stride))) return rc;
   }
-  int rc;
-  if ((rc = dev_alloc(e, &e->d_partial, (size_t)(256 * 4) * (((size_t)e->part_stride + 15) / 16 * 16)))) return rc;      // [entry / 16][workgroup][16]
-  if ((rc = dev_alloc(e, &e->d_red, (size_t)pba_engine::kChunks * e->part_stride))) return rc;
-  if ((rc = dev_alloc(e, &e->d_packed, (size_t)e->part_stride))) return rc;
   if (e->solve_tab_nf != e->n_free) {
     std::vector<uint32_t> tab((size_t)solve_table_words(e->n_free));
     solve_tables(e->n_free, tab.data());
@@ -1175,6 +1319,8 @@ int pba_get_state(pba_engine* e, double* cams6, double* xyz) {
 int pba_set_inverse_depth(pba_engine* e, const double* rays6, const double* rho) {
   if (!e || !rays6 || !rho) return PBA_ERR_INVALID;
   if (!e->have_problem) return fail(e, PBA_ERR_STATE, "call order violated: pba_set_inverse_depth before pba_set_problem");
+  if (e->have_cams && e->wide)
+    return fail(e, PBA_ERR_INVALID, "pba_set_inverse_depth: the inverse-depth mode is not built for wide windows (%d free cameras)", e->n_free);
   PBA_NOT_POISONED(e);
   HIP_TRY(e, hipSetDevice(e->cfg.device));
   const int n = e->n_points;
@@ -1266,13 +1412,18 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
   sc.jacobi = o->jacobi_scaling; sc.fx = e->cfg.fx; sc.fy = e->cfg.fy; sc.radius = radius; sc.inv_radius = 1.0 / radius;
   sc.min_diag = o->min_lm_diagonal; sc.max_diag = o->max_lm_diagonal;
   sc.dbg = nullptr; sc.lm = nullptr;
-  if (e->dbg_left > 0) {
+  if (e->dbg_left > 0 && !e->wide) {
     if (!e->d_dbg) { (void)hipMalloc(reinterpret_cast<void**>(&e->d_dbg), sizeof(unsigned long long) * 8 * (1024 + 4096)); }
     sc.dbg = e->d_dbg;
   }
-  ev_begin(e, 2);
-  launch_schur(e, sc);
-  ev_end(e, 2);
+  if (e->wide) {
+    const int rcw = wide_eliminate(e, cur, init_scale, o, radius);
+    if (rcw) return rcw;
+  } else {
+    ev_begin(e, 2);
+    launch_schur(e, sc);
+    ev_end(e, 2);
+  }
   if (sc.dbg) {
     std::vector<unsigned long long> h(8 * (size_t)e->schur_grid);
     (void)hipMemcpyAsync(h.data(), e->d_dbg, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, e->stream);
@@ -1305,7 +1456,15 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
   so.max_diag = o->max_lm_diagonal;
   so.lm = nullptr;
   so.dbg = (e->dbg_left > 0) ? 1 : 0;
-  { const int rcs = launch_reduce_and_solve(e, so, n, cur, cand, nullptr, 0, e->cost_blocks[cur]); if (rcs) return rcs; }
+  if (e->wide) {
+    ev_begin(e, 3);
+    hipLaunchKernelGGL(k_solve_wide, dim3(1), dim3(kSolveWideT), solve_wide_smem_bytes(n), e->stream, so);
+    ev_end(e, 3);
+    HIP_TRY(e, hipGetLastError());
+  } else {
+    const int rcs = launch_reduce_and_solve(e, so, n, cur, cand, nullptr, 0, e->cost_blocks[cur]);
+    if (rcs) return rcs;
+  }
   const unsigned long long seq = ++e->seq;
   unsigned long long* h_seq_dev = reinterpret_cast<unsigned long long*>(e->h_scal_dev + kNumScal);
   bool xchg_packed = false;
@@ -1495,6 +1654,8 @@ int pba_comm_unique_id(void* id128) { return Comm::unique_id(id128) ? PBA_ERR_CO
 
 int pba_comm_init_rccl(pba_engine* e, const void* id128, int32_t rank, int32_t world) {
   if (!e || !id128 || world < 1 || rank < 0 || rank >= world) return PBA_ERR_INVALID;
+  if (world > 1 && e->have_cams && e->wide)
+    return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for wide windows (%d free cameras)", e->n_free);
   PBA_NOT_POISONED(e);
   HIP_TRY(e, hipSetDevice(e->cfg.device));
   if (e->comm.init_rccl(id128, rank, world)) return fail(e, PBA_ERR_COMM, "%s", e->comm.err.c_str());
@@ -1503,6 +1664,8 @@ int pba_comm_init_rccl(pba_engine* e, const void* id128, int32_t rank, int32_t w
 
 int pba_comm_init_callback(pba_engine* e, pba_allreduce_fn fn, void* ctx, int32_t rank, int32_t world) {
   if (!e || !fn || world < 1 || rank < 0 || rank >= world) return PBA_ERR_INVALID;
+  if (world > 1 && e->have_cams && e->wide)
+    return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for wide windows (%d free cameras)", e->n_free);
   PBA_NOT_POISONED(e);
   HIP_TRY(e, hipSetDevice(e->cfg.device));
   if (e->comm.init_callback(fn, ctx, rank, world)) return fail(e, PBA_ERR_COMM, "%s", e->comm.err.c_str());

@@ -101,14 +101,15 @@ __device__ __forceinline__ double readlane_f64(double v, int src_lane) {
 // Cooperative copy of the per-camera geometry table into LDS (8-byte words, coalesced): the per-lane gathers of
 // ~50 doubles per observation then hit LDS instead of going through the vector memory path.
 // AG: the table was written by another workgroup of the SAME launch (resident solve): agent-scope loads
-template <int NT, bool AG = false>
+// MF: length of the destination table (kMaxFrames, or kMaxFramesWide for the wide-window instantiations)
+template <int NT, bool AG = false, int MF = kMaxFrames>
 __device__ __forceinline__ void stage_geom(const CamGeom* __restrict__ src, CamGeom* dst, int n_frames, int tid) {
   static_assert(sizeof(CamGeom) % 8 == 0, "CamGeom is copied as 8-byte words");
   const unsigned long long* s = reinterpret_cast<const unsigned long long*>(src);
   unsigned long long* d = reinterpret_cast<unsigned long long*>(dst);
   const int n = n_frames * (int)(sizeof(CamGeom) / 8);
   // all loads of the thread in flight together (the rolled loop paid one L2 round trip per trip: 2 at 8 frames, 4 at 16)
-  constexpr int IT = (kMaxFrames * (int)(sizeof(CamGeom) / 8) + NT - 1) / NT;
+  constexpr int IT = (MF * (int)(sizeof(CamGeom) / 8) + NT - 1) / NT;
   unsigned long long v[IT];
 #pragma unroll
   for (int u = 0; u < IT; ++u) {
@@ -1191,13 +1192,13 @@ constexpr int sample_stage_groups(int ng, int per_group) {
 constexpr int kSampleLdsStride = 65;
 struct SampleIrrRec { double u, v; int32_t wyx, pt, src, pad; };
 constexpr int kSampleIrrCap = 32;
-template <int R, int WAVES>
+template <int R, int WAVES, int MF = kMaxFrames>
 struct SampleSmem {
   static constexpr int F = 2 * R + 2;
   static constexpr int RB = sample_rows_per_batch(R);
   static constexpr int FF = RB * F;                      // texels of one batch
   static constexpr size_t kTexBytes = sizeof(uint32_t) * WAVES * FF * kSampleLdsStride;
-  static constexpr size_t kPreBytes = sizeof(double) * 3 * WAVES * 64 + 2 * kMaxFrames * sizeof(CamGeom);
+  static constexpr size_t kPreBytes = sizeof(double) * 3 * WAVES * 64 + 2 * MF * sizeof(CamGeom);
   static_assert(kTexBytes >= sizeof(double) * 4 * WAVES * 64, "the finalisation reuses the texel region");
   alignas(16) char raw[kTexBytes > kPreBytes ? kTexBytes : kPreBytes];
   alignas(8) int32_t bi[2][WAVES][64];
@@ -1229,13 +1230,14 @@ struct ResLane {
 //   RES: phase of the resident solve -- indices, points, previous records and descriptors come from `rl`, the candidate point and
 //        its records go back there; tables produced by other workgroups of the SAME launch are read with agent-scope loads; the
 //        step finalisation (ticket, fixed-order reduction, decision) is the caller's.
-template <int R, bool JAC, int WAVES, bool FUSED, bool UNITW, bool FAST, bool RES>
+template <int R, bool JAC, int WAVES, bool FUSED, bool UNITW, bool FAST, bool RES, int MF = kMaxFrames>
 // tix = threadIdx.x (the resident solve passes it through an opaque copy per trip of its loop: with the plain builtin the compiler
 // hoists every per-lane address and mask of every phase out of the loop -- hundreds of registers live across all of it)
-__device__ __forceinline__ void sample_wg(SampleParams& p, SampleSmem<R, WAVES>& sm, ResLane<R>& rl, const int bid, const int n_blocks, const int tix, CamGeom* geom_lds = nullptr) {
+__device__ __forceinline__ void sample_wg(SampleParams& p, SampleSmem<R, WAVES, MF>& sm, ResLane<R>& rl, const int bid, const int n_blocks, const int tix, CamGeom* geom_lds = nullptr) {
   static_assert(!FUSED || (WAVES * 64) % 128 == 0, "fused tiles are 128 observations");
   static_assert(!FAST || UNITW, "the reduced-precision walk assumes unit patch weights");
   static_assert(!RES || (FUSED && !FAST), "the resident phase is the fused exact kernel");
+  static_assert(MF == kMaxFrames || !FUSED, "the wide-window tables (MF > kMaxFrames) are for the unfused chain");
   // inverse-depth variant (point_world): null for the reference's free world points
   const double* rays = p.rays;
   constexpr int W = 2 * R + 1;      // patch side
@@ -1266,7 +1268,7 @@ __device__ __forceinline__ void sample_wg(SampleParams& p, SampleSmem<R, WAVES>&
   // camera geometry tables -> LDS (the texel region is free until the staging phase)
   // (resident solve: the table of the point being sampled goes to the workgroup's PERSISTENT copy, which the next elimination reads)
   CamGeom* s_geom = RES ? geom_lds : reinterpret_cast<CamGeom*>(s_raw + sizeof(double) * 3 * WAVES * 64);
-  double* s_bk = reinterpret_cast<double*>(reinterpret_cast<CamGeom*>(s_raw + sizeof(double) * 3 * WAVES * 64) + kMaxFrames);
+  double* s_bk = reinterpret_cast<double*>(reinterpret_cast<CamGeom*>(s_raw + sizeof(double) * 3 * WAVES * 64) + MF);
   unsigned long long tk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long tl = p.dbg ? __builtin_amdgcn_s_memtime() : 0;
   const unsigned long long t_begin = p.dbg ? __builtin_amdgcn_s_memrealtime() : 0;   // 100 MHz, device-wide
@@ -1278,7 +1280,7 @@ __device__ __forceinline__ void sample_wg(SampleParams& p, SampleSmem<R, WAVES>&
   else if (FUSED) fi = fused_prefetch_indices<WAVES * 64>(p, bid, tix);
   // (resident solve, step trips: p.geom == null -- the candidate table is in `geom_lds` already, polled there from the solve's tagged words,
   // and geom_prev / delta_c name LDS copies; its first linearisation stages the initial table from global memory like everybody else)
-  if (!RES || p.geom) stage_geom<WAVES * 64, RES>(p.geom, s_geom, p.n_frames, tix);
+  if (!RES || p.geom) stage_geom<WAVES * 64, RES, MF>(p.geom, s_geom, p.n_frames, tix);
   if (FUSED) fused_stage_step_table<WAVES * 64, false>(p, s_bk, tix);
   lds_barrier();
   PBA_STK(0);
@@ -1840,7 +1842,8 @@ __device__ __forceinline__ void sample_wg(SampleParams& p, SampleSmem<R, WAVES>&
 
 // amdgpu_waves_per_eu(N, N): the register allocator / scheduler works for exactly N resident waves per SIMD (with only a
 // lower bound it trades instruction-level parallelism for an occupancy the kernel does not profit from: measured).
-template <int R, bool JAC, int WAVES, bool FUSED, bool UNITW, bool FAST>
+// MF: camera-table length (kMaxFrames; kMaxFramesWide for the wide-window chain, unfused only)
+template <int R, bool JAC, int WAVES, bool FUSED, bool UNITW, bool FAST, int MF = kMaxFrames>
 __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu((R <= 2 ? (JAC ? PBA_SAMPLE_WAVES_PER_SIMD : 2) : (R >= 4 ? PBA_SAMPLE_WAVES_LARGE : 2)), (R <= 2 ? (JAC ? PBA_SAMPLE_WAVES_PER_SIMD : 2) : (R >= 4 ? PBA_SAMPLE_WAVES_LARGE : 2)))))
 void k_sample(SampleParams p_in) {
   SampleParams p = p_in;
@@ -1848,9 +1851,9 @@ void k_sample(SampleParams p_in) {
   if (FUSED && !fused_resolve_parity(p)) return;
   if (FUSED && p.lm_init_dst && blockIdx.x == 0 && threadIdx.x < sizeof(LmState) / 4)      // (consumed by the NEXT kernel of the stream)
     reinterpret_cast<unsigned*>(p.lm_init_dst)[threadIdx.x] = __hip_atomic_load(reinterpret_cast<const unsigned*>(p.lm_init_src) + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __shared__ SampleSmem<R, WAVES> sm;
+  __shared__ SampleSmem<R, WAVES, MF> sm;
   ResLane<R> unused;      // (three-kernel path: nothing is resident)
-  sample_wg<R, JAC, WAVES, FUSED, UNITW, FAST, false>(p, sm, unused, xcd_logical_block(blockIdx.x, gridDim.x), (int)gridDim.x, (int)threadIdx.x);
+  sample_wg<R, JAC, WAVES, FUSED, UNITW, FAST, false, MF>(p, sm, unused, xcd_logical_block(blockIdx.x, gridDim.x), (int)gridDim.x, (int)threadIdx.x);
 }
 
 // =====================================================================================================
@@ -2069,9 +2072,10 @@ constexpr int sample_mc_rows_per_batch(int R) { return R == 2 ? PBA_MC_RB2 : (((
 //   FUSED: like k_sample's fused form -- back-substitution of the step for the workgroup's whole points first, sampling at
 //   the candidate it just formed, step finalisation (and, single rank, the trust-region decision) by the last workgroup.
 //   UNITW: unit patch weights (MakePatchWeights without the Gaussian, the reference's default): w^2 = 1 is folded away.
-template <int R, bool JAC, int WAVES, bool FUSED, bool UNITW>
+template <int R, bool JAC, int WAVES, bool FUSED, bool UNITW, int MF = kMaxFrames>
 __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(PBA_MC_WAVES(R), PBA_MC_WAVES(R)))) void k_sample_mc(SampleParams p_in, const float* __restrict__ frames_mc, int n_channels) {
   static_assert(!FUSED || (WAVES * 64) % 128 == 0, "fused tiles are 128 observations");
+  static_assert(MF == kMaxFrames || !FUSED, "the wide-window tables (MF > kMaxFrames) are for the unfused chain");
   SampleParams p = p_in;
   p.dbg = nullptr;
   if (FUSED && !fused_resolve_parity(p)) return;
@@ -2088,7 +2092,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(PBA_
   constexpr int NPL = JAC ? 3 : 1;
   constexpr size_t kTexBytes = sizeof(float) * WAVES * FF * LSTRIDE;
   constexpr size_t kBsBytes = FUSED ? sizeof(double) * 3 * WAVES * 64 : 0;      // back-substitution scratch ahead of the tables
-  constexpr size_t kPreBytes = kBsBytes + (FUSED ? 2 : 1) * kMaxFrames * sizeof(CamGeom);
+  constexpr size_t kPreBytes = kBsBytes + (FUSED ? 2 : 1) * MF * sizeof(CamGeom);
   static_assert(!FUSED || kTexBytes >= sizeof(double) * 4 * WAVES * 64, "the finalisation reuses the texel region");
   __shared__ __attribute__((aligned(16))) char s_raw[kTexBytes > kPreBytes ? kTexBytes : kPreBytes];
   float (*s_tex)[FF * LSTRIDE] = reinterpret_cast<float (*)[FF * LSTRIDE]>(s_raw);
@@ -2101,10 +2105,10 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(PBA_
   bool active = obs < p.n_obs;
   if (threadIdx.x == 0) s_fail = 0;
   CamGeom* s_geom = reinterpret_cast<CamGeom*>(s_raw + kBsBytes);
-  double* s_bk = reinterpret_cast<double*>(s_geom + kMaxFrames);
+  double* s_bk = reinterpret_cast<double*>(s_geom + MF);
   FusedIdx fi{make_int4(0, 0, 0, 0), 0, 0, 0, 0};
   if (FUSED) fi = fused_prefetch_indices<WAVES * 64>(p, bid, (int)threadIdx.x);
-  stage_geom<WAVES * 64>(p.geom, s_geom, p.n_frames, threadIdx.x);
+  stage_geom<WAVES * 64, false, MF>(p.geom, s_geom, p.n_frames, threadIdx.x);
   if (FUSED) fused_stage_step_table<WAVES * 64>(p, s_bk, (int)threadIdx.x);
   lds_barrier();
 
