@@ -281,6 +281,20 @@ int pba_get_obs_records(pba_engine* e, double* rec6);
 int pba_solve(pba_engine* e, const pba_solver_options* o, pba_solver_summary* summary,
               pba_iteration_summary* iterations, int32_t max_iterations_out);
 
+/* ---- several independent windows on one device ------------------------------------------------------------ */
+#define PBA_MAX_BATCH 64
+/* Solves n independent windows together: one launch of each phase of a pipelined LM iteration serves every window still running.
+ * Each window's result equals its own pba_solve bit for bit (summary, iteration log, cameras, points; wall-clock fields aside).
+ * options: [n] or NULL for the defaults of pba_default_solver_options; summaries: [n]; iterations: [n][max_iterations_out] or NULL.
+ * Every check comes before any device call; PBA_ERR_INVALID / PBA_ERR_STATE refuse the whole batch, with the offending index and the
+ * reason in pba_last_error of engines[0] and of that engine:  1 <= n <= PBA_MAX_BATCH; engines non-null, each once, all on one device;
+ * every engine ready (PBA_ERR_STATE), single-rank, narrow (<= 15 free cameras), without the precision-sweep flags or profiling, with
+ * options the pipelined driver takes; one kernel key (patch radius, channel count, unit or Gaussian weights) for all.  Windows may differ
+ * in everything else (image size, K, points, frames, fixed slot, Huber threshold, options, inverse depth).  Synchronous like pba_solve;
+ * afterwards pba_solve_driver names "batched".  A timed-out wait makes every engine of the batch unusable. */
+int pba_solve_batch(pba_engine* const* engines, int32_t n, const pba_solver_options* options,
+                    pba_solver_summary* summaries, pba_iteration_summary* iterations, int32_t max_iterations_out);
+
 /* ---- multi-GPU: points are sharded across ranks, one all-reduce of the reduced camera system per solve --- */
 /* RCCL transport (one process per GPU): rank 0 calls pba_comm_unique_id, broadcasts the 128 bytes out of band. */
 int pba_comm_unique_id(void* id128);
@@ -312,8 +326,8 @@ int pba_reset_counters(pba_engine* e);
 /* Which driver ran the LAST pba_solve: "resident" (the whole solve as ONE cooperative launch, every workgroup keeping its tiles'
  * state in registers across the iterations: windows that fit one resident round of workgroups -- <= 2 x 128 observations per CU --
  * on a single rank, patch radius <= 2, <= 8 free cameras; PBA_RESIDENT=0 switches it off), "pipelined" (three kernels per
- * iteration enqueued ahead of the device-side decisions), "host-stepped" (PBA_ASYNC=0, event profiling), "none".  The three take
- * the same decisions on the same numbers; "resident" and "pipelined" are bit-identical. */
+ * iteration enqueued ahead of the device-side decisions), "host-stepped" (PBA_ASYNC=0, event profiling), "batched" (pba_solve_batch),
+ * "none".  They take the same decisions on the same numbers; "resident", "pipelined" and "batched" are bit-identical. */
 const char* pba_solve_driver(const pba_engine* e);
 
 #ifdef __cplusplus

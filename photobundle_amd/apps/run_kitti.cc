@@ -12,6 +12,7 @@
 //     DepthSource = stereo   depth from the left/right pair on the device: the config's StereoAlgorithm (BlockMatching) +
 //                            disparityToDepth with Bf = baseline * fx (reference apps/run_kitti.cc:29, src/dataset.cc:105-137)
 #include <algorithm>
+#include <array>
 #include <cctype>
 #include <csignal>
 #include <cstdio>
@@ -94,70 +95,160 @@ static void dumpResult(const std::string& fn, int frame, const PhotometricBundle
   std::fclose(f);
 }
 
+// One sequence: its config, data, initial trajectory and depth source (what main() reads for the single run, and per -b entry)
+struct Sequence {
+  std::unique_ptr<utils::ConfigFile> cf;
+  std::string data, depth_source, output, results;
+  Calibration calib;
+  EigenAlignedContainer_<Mat44> T_init;
+  std::vector<uint8_t> img, right;
+  std::vector<float> depth;
+  int rows = 0, cols = 0, num_levels = 1;
+  float Bf = 0.f;
+  std::unique_ptr<StereoAlgorithm> stereo;
+
+  explicit Sequence(const std::string& config) : cf(new utils::ConfigFile(config)) {
+    data = cf->get<std::string>("DataDirectory");
+    calib = loadCalibration(data + "/calib.txt");
+    depth_source = cf->get<std::string>("DepthSource", "files");
+    std::transform(depth_source.begin(), depth_source.end(), depth_source.begin(), [](unsigned char c) { return std::tolower(c); });
+    if (depth_source != "files" && depth_source != "stereo") throw std::runtime_error("DepthSource must be files or stereo, not " + depth_source);
+    T_init = loadPosesKittiFormat(cf->get<std::string>("trajectory"));
+    char name[64];
+    std::snprintf(name, sizeof(name), "/image_%06d.pgm", 0);
+    if (!readPgm(data + name, img, rows, cols)) throw std::runtime_error("cannot read the first frame");
+    Bf = (float)(calib.b() * calib.fx());
+    num_levels = cf->get<int>("numLevels", 1);   // > 1: coarse-to-fine (photobundle_pyramid path)
+  }
+  void start() { if (depth_source == "stereo") stereo.reset(new StereoAlgorithm(*cf)); }
+  // frame f_i into img / depth; false when the image is missing (the sequence ends)
+  bool read(int f_i) {
+    char name[64];
+    std::snprintf(name, sizeof(name), "/image_%06d.pgm", f_i);
+    int r2, c2;
+    if (!readPgm(data + name, img, r2, c2)) return false;
+    if (r2 != rows || c2 != cols) throw std::runtime_error("frame size changed");
+    depth.resize((size_t)rows * cols);
+    if (stereo) {
+      std::snprintf(name, sizeof(name), "/right_%06d.pgm", f_i);
+      if (!readPgm(data + name, right, r2, c2)) throw std::runtime_error(std::string("cannot read ") + (name + 1));
+      if (r2 != rows || c2 != cols) throw std::runtime_error("right frame size differs");
+      stereo->depth(img.data(), right.data(), ImageSize(rows, cols), Bf, depth.data());
+    } else {
+      std::snprintf(name, sizeof(name), "/depth_%06d.bin", f_i);
+      std::ifstream dfs(data + name, std::ios::binary);
+      if (!dfs.read(reinterpret_cast<char*>(depth.data()), depth.size() * sizeof(float))) throw std::runtime_error("bad depth file");
+    }
+    return true;
+  }
+};
+
+static void writePoses(const std::string& output, const PhotometricBundleAdjustment::Result& result, bool full_precision) {
+  std::fprintf(stderr, "Writing refined poses to %s\n", output.c_str());
+  if (full_precision) writePosesKittiFormatFullPrecision(output, result.poses);
+  else writePosesKittiFormat(output, result.poses);   // reference format (src/pose_utils.cc:43-59)
+}
+
+// -b: several sequences from one process.  They advance in lockstep, one frame each, then one batched optimisation
+// (PhotometricBundleAdjustment::addFrames); a sequence leaves when its frames or its trajectory run out.
+static int runBatch(std::vector<std::unique_ptr<Sequence>>& seqs, bool full_precision) {
+  for (auto& q : seqs)
+    if (q->num_levels > 1) { std::fprintf(stderr, "error: -b takes single-level configs only (%s: numLevels = %d)\n", q->output.c_str(), q->num_levels); return 1; }
+  std::vector<std::unique_ptr<PhotometricBundleAdjustment>> pb;
+  std::vector<PhotometricBundleAdjustment::Result> res(seqs.size());
+  std::vector<bool> live(seqs.size(), true);
+  for (auto& q : seqs) { q->start(); pb.emplace_back(new PhotometricBundleAdjustment(q->calib, ImageSize(q->rows, q->cols), {*q->cf})); }
+  for (int f_i = 0; !gStop; ++f_i) {
+    std::vector<PhotometricBundleAdjustment*> inst;
+    std::vector<PhotometricBundleAdjustment::Frame> frames;
+    std::vector<PhotometricBundleAdjustment::Result*> out;
+    std::vector<size_t> idx;
+    for (size_t k = 0; k < seqs.size(); ++k) {
+      if (!live[k]) continue;
+      if (f_i >= (int)seqs[k]->T_init.size() || !seqs[k]->read(f_i)) { live[k] = false; writePoses(seqs[k]->output, res[k], full_precision); continue; }
+      res[k].initialCost = -1.0;
+      inst.push_back(pb[k].get());
+      frames.push_back({seqs[k]->img.data(), seqs[k]->depth.data(), &seqs[k]->T_init[f_i]});
+      out.push_back(&res[k]);
+      idx.push_back(k);
+    }
+    if (inst.empty()) break;
+    std::printf("Frame %05d (%zu sequences)\n", f_i, inst.size());
+    PhotometricBundleAdjustment::addFrames(inst, frames, out);
+    for (size_t k : idx)
+      if (!seqs[k]->results.empty() && res[k].initialCost >= 0.0) dumpResult(seqs[k]->results, f_i, res[k]);
+  }
+  for (size_t k = 0; k < seqs.size(); ++k) if (live[k]) writePoses(seqs[k]->output, res[k], full_precision);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   signal(SIGINT, sigHandler);
   // -r (not in the reference's driver): text dump of every Result the class hands back (reference photobundle.cc:857-875)
   // -p (not in the reference's driver): poses with round-trip precision instead of the reference's 6 significant digits
+  // -b CONFIG:OUTPUT[:RESULTS] (not in the reference's driver, repeatable): several sequences from one process (runBatch)
   std::string config = "../config/kitti_stereo.cfg", output = "refined_poses.txt", results;
-  bool full_precision = false;
+  bool full_precision = false, single_opts = false;
+  std::vector<std::string> batch;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
-    if ((a == "-c" || a == "--config") && i + 1 < argc) config = argv[++i];
-    else if ((a == "-o" || a == "--output") && i + 1 < argc) output = argv[++i];
-    else if ((a == "-r" || a == "--results") && i + 1 < argc) results = argv[++i];
+    if ((a == "-c" || a == "--config") && i + 1 < argc) { config = argv[++i]; single_opts = true; }
+    else if ((a == "-o" || a == "--output") && i + 1 < argc) { output = argv[++i]; single_opts = true; }
+    else if ((a == "-r" || a == "--results") && i + 1 < argc) { results = argv[++i]; single_opts = true; }
     else if (a == "-p" || a == "--full-precision") full_precision = true;
-    else { std::fprintf(stderr, "usage: %s [-c config] [-o output] [-r result-dump] [-p]\n", argv[0]); return 1; }
+    else if ((a == "-b" || a == "--batch") && i + 1 < argc) batch.push_back(argv[++i]);
+    else { std::fprintf(stderr, "usage: %s [-c config] [-o output] [-r result-dump] [-p]  |  %s -b config:output[:result-dump] [-b ...] [-p]\n", argv[0], argv[0]); return 1; }
+  }
+  if (!batch.empty()) {
+    if (single_opts) { std::fprintf(stderr, "error: -b names each sequence's config, output and result dump; it does not combine with -c, -o or -r\n"); return 1; }
+    std::vector<std::array<std::string, 3>> specs;
+    for (const std::string& b : batch) {
+      std::array<std::string, 3> f;
+      size_t n_f = 0, pos = 0;
+      while (n_f < 3) {
+        const size_t c = b.find(':', pos);
+        f[n_f++] = b.substr(pos, c == std::string::npos ? std::string::npos : c - pos);
+        if (c == std::string::npos) break;
+        pos = c + 1;
+        if (n_f == 3) { n_f = 4; break; }
+      }
+      if (n_f < 2 || n_f > 3 || f[0].empty() || f[1].empty() || (n_f == 3 && f[2].empty())) {
+        std::fprintf(stderr, "error: -b takes CONFIG:OUTPUT[:RESULTS], got \"%s\"\n", b.c_str());
+        return 1;
+      }
+      specs.push_back(f);
+    }
+    try {
+      std::vector<std::unique_ptr<Sequence>> seqs;
+      for (const auto& f : specs) {
+        seqs.emplace_back(new Sequence(f[0]));
+        seqs.back()->output = f[1];
+        seqs.back()->results = f[2];
+      }
+      return runBatch(seqs, full_precision);
+    } catch (const std::exception& ex) {
+      std::fprintf(stderr, "error: %s\n", ex.what());
+      return 1;
+    }
   }
   try {
-    utils::ConfigFile cf(config);
-    const std::string data = cf.get<std::string>("DataDirectory");
-    const Calibration calib = loadCalibration(data + "/calib.txt");
-    std::string depth_source = cf.get<std::string>("DepthSource", "files");
-    std::transform(depth_source.begin(), depth_source.end(), depth_source.begin(), [](unsigned char c) { return std::tolower(c); });
-    if (depth_source != "files" && depth_source != "stereo") throw std::runtime_error("DepthSource must be files or stereo, not " + depth_source);
-    const auto T_init = loadPosesKittiFormat(cf.get<std::string>("trajectory"));
-
-    std::vector<uint8_t> img, right;
-    std::vector<float> depth;
-    int rows = 0, cols = 0;
-    char name[64];
-    std::snprintf(name, sizeof(name), "/image_%06d.pgm", 0);
-    if (!readPgm(data + name, img, rows, cols)) throw std::runtime_error("cannot read the first frame");
-    std::unique_ptr<StereoAlgorithm> stereo;
-    const float Bf = (float)(calib.b() * calib.fx());
-    if (depth_source == "stereo") stereo.reset(new StereoAlgorithm(cf));
-
+    Sequence q(config);
+    q.start();
+    const int rows = q.rows, cols = q.cols;
     PhotometricBundleAdjustment::Result result;
-    const int num_levels = cf.get<int>("numLevels", 1);   // > 1: coarse-to-fine (photobundle_pyramid path)
     std::unique_ptr<PhotometricBundleAdjustment> photoba;
     std::unique_ptr<PhotometricBundleAdjustmentPyr> photoba_pyr;
-    if (num_levels > 1) photoba_pyr.reset(new PhotometricBundleAdjustmentPyr(num_levels, calib, ImageSize(rows, cols), {cf}));
-    else photoba.reset(new PhotometricBundleAdjustment(calib, ImageSize(rows, cols), {cf}));
-    for (int f_i = 0; f_i < (int)T_init.size() && !gStop; ++f_i) {
-      std::snprintf(name, sizeof(name), "/image_%06d.pgm", f_i);
-      int r2, c2;
-      if (!readPgm(data + name, img, r2, c2)) break;
-      if (r2 != rows || c2 != cols) throw std::runtime_error("frame size changed");
-      depth.resize((size_t)rows * cols);
-      if (stereo) {
-        std::snprintf(name, sizeof(name), "/right_%06d.pgm", f_i);
-        if (!readPgm(data + name, right, r2, c2)) throw std::runtime_error(std::string("cannot read ") + (name + 1));
-        if (r2 != rows || c2 != cols) throw std::runtime_error("right frame size differs");
-        stereo->depth(img.data(), right.data(), ImageSize(rows, cols), Bf, depth.data());
-      } else {
-        std::snprintf(name, sizeof(name), "/depth_%06d.bin", f_i);
-        std::ifstream dfs(data + name, std::ios::binary);
-        if (!dfs.read(reinterpret_cast<char*>(depth.data()), depth.size() * sizeof(float))) throw std::runtime_error("bad depth file");
-      }
+    if (q.num_levels > 1) photoba_pyr.reset(new PhotometricBundleAdjustmentPyr(q.num_levels, q.calib, ImageSize(rows, cols), {*q.cf}));
+    else photoba.reset(new PhotometricBundleAdjustment(q.calib, ImageSize(rows, cols), {*q.cf}));
+    for (int f_i = 0; f_i < (int)q.T_init.size() && !gStop; ++f_i) {
+      if (!q.read(f_i)) break;
       std::printf("Frame %05d\n", f_i);
       result.initialCost = -1.0;    // the class only touches `result` when an optimisation ran (photobundle.cc:857)
-      if (photoba_pyr) photoba_pyr->addFrame(img.data(), depth.data(), T_init[f_i], &result);
-      else photoba->addFrame(img.data(), depth.data(), T_init[f_i], &result);
+      if (photoba_pyr) photoba_pyr->addFrame(q.img.data(), q.depth.data(), q.T_init[f_i], &result);
+      else photoba->addFrame(q.img.data(), q.depth.data(), q.T_init[f_i], &result);
       if (!results.empty() && result.initialCost >= 0.0) dumpResult(results, f_i, result);
     }
-    std::fprintf(stderr, "Writing refined poses to %s\n", output.c_str());
-    if (full_precision) writePosesKittiFormatFullPrecision(output, result.poses);
-    else writePosesKittiFormat(output, result.poses);   // reference format (src/pose_utils.cc:43-59)
+    writePoses(output, result, full_precision);
   } catch (const std::exception& ex) {
     std::fprintf(stderr, "error: %s\n", ex.what());
     return 1;

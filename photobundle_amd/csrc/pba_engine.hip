@@ -10,6 +10,7 @@
 #include "pba_frontend.h"
 #include "pba_resident.h"
 #include "pba_wide.h"
+#include "pba_batch.h"
 
 #include <algorithm>
 #include <chrono>
@@ -132,7 +133,7 @@ struct pba_engine {
   int res_groups_n[2][2] = {{-1, -1}, {-1, -1}};     // ... the reduced-system size that answer was given for
   int n_cus = 0, coop_launch = 0;
   int64_t res_launches = 0;
-  int last_driver = 0;              // 0 none, 1 resident, 2 pipelined, 3 host-stepped (pba_solve_driver)
+  int last_driver = 0;              // 0 none, 1 resident, 2 pipelined, 3 host-stepped, 4 batched (pba_solve_driver)
   double wait_timeout_s = 120.0;    // PBA_WAIT_TIMEOUT_S: watchdog of the publication waits
   double tick_hz = 1e8;             // rate of s_memrealtime (hipDeviceAttributeWallClockRate; 100 MHz on gfx950): device-side time-outs
   bool poisoned = false;            // a publication wait timed out: the stream still holds the stalled work, every later
@@ -153,6 +154,14 @@ struct pba_engine {
   int32_t* d_wpair_chunk = nullptr; // [n_pairs + 1]
   double* d_wsums = nullptr;        // [wide_chunks][kWideVals]
   int wide_chunks = 0, wide_pt_blocks = 0;
+
+  // batched solves (pba_solve_batch, pba_batch.h): the window table lives with the batch's FIRST engine (grow-only), whose stream
+  // carries the batch; while a batch runs every engine's `stream` names that stream and `stream_own` keeps its own
+  BatchWindow* d_batch = nullptr;
+  BatchWindow* h_batch = nullptr;   // pinned staging of the table
+  int batch_cap = 0;                // windows
+  hipStream_t stream_own = nullptr;
+  int batch_init2 = 0;              // init_scale of this window's final pass (max_num_iterations <= 0)
 
   Comm comm;
   unsigned int* h_comm_err = nullptr;      // host-mapped: a peer-exchange wait timed out (k_peer_allreduce)
@@ -234,6 +243,7 @@ int check_ready(pba_engine* e, const char* who) {
 }
 
 constexpr int kSampleWaves = 4;    // 256-thread workgroups at every patch radius (two 128-observation tiles when fused)
+static_assert(kBatchSampleWaves == kSampleWaves && kMaxBatch == PBA_MAX_BATCH, "the batched launches run the solo workgroups");
 
 // MF: camera-table length of the sampling kernels -- kMaxFrames, or kMaxFramesWide on wide windows (unfused, exact precision only:
 // pba_set_cameras refuses the sweep modes there)
@@ -371,35 +381,48 @@ int peer_allreduce(pba_engine* e, int kind, int n, double* out) {
 // exchange of the packed sums sits between the two, so they stay separate kernels.  With the peer exchange there is no
 // exchange kernel: the reduction's last workgroup raises this rank's mailbox flag, the solve's prologue waits for every
 // rank's flag and sums the mailbox slots in rank order (pba_solve.h).
-int launch_reduce_and_solve(pba_engine* e, SolveParams so, int n, int cur, int cand, const LmState* lm, int final_pass, int n_cost_blocks,
-                            const ReduceSolveParams::Fin* fin = nullptr) {
-  const bool multi = e->comm.multi();
-  // The gradient-only pass neither forms nor reduces the pair blocks and the right-hand side: the reduced-system test hook
-  // (pba_get_reduced_system) keeps the system of the last FULL step instead of being overwritten with entries nobody computed
-  if (final_pass && !so.init_scale) { so.S_dbg = nullptr; so.rhs_dbg = nullptr; }
-  const int grid = (e->part_stride + kReduceEntries - 1) / kReduceEntries + 1;
-  const int pstride = packed_stride(n);
+int reduce_grid(const pba_engine* e) { return (e->part_stride + kReduceEntries - 1) / kReduceEntries + 1; }
+ReduceParams reduce_params(pba_engine* e, int cur, int n_cost_blocks) {
   ReduceParams rp{};
   rp.partial = e->d_partial; rp.n_blocks = e->schur_grid; rp.stride = e->part_stride; rp.n_free = e->n_free; rp.n_pairs = e->n_pairs;
   rp.block_cost = e->d_block_cost[cur]; rp.block_fail = e->d_block_fail[cur]; rp.n_cost_blocks = n_cost_blocks;
   rp.packed = e->d_packed; rp.scal = e->d_scal;
+  return rp;
+}
+// parameters of the single-rank k_reduce_solve (the solo launch below and the batched one, pba_batch.h)
+ReduceSolveParams reduce_solve_params(pba_engine* e, SolveParams so, int n, int cur, int cand, const LmState* lm, int final_pass, int n_cost_blocks,
+                                      const ReduceSolveParams::Fin* fin) {
+  // The gradient-only pass neither forms nor reduces the pair blocks and the right-hand side: the reduced-system test hook
+  // (pba_get_reduced_system) keeps the system of the last FULL step instead of being overwritten with entries nobody computed
+  if (final_pass && !so.init_scale) { so.S_dbg = nullptr; so.rhs_dbg = nullptr; }
+  ReduceSolveParams rsp{};
+  rsp.rp = reduce_params(e, cur, n_cost_blocks);
+  rsp.block_cost_alt = e->d_block_cost[cand]; rsp.block_fail_alt = e->d_block_fail[cand];
+  rsp.ticket = e->d_ticket_solve; rsp.so = so;
+  if (fin) {
+    rsp.fin = *fin;
+    // gradient-only: the pair blocks and the right-hand side of the partials are not consumed
+    if (final_pass && !so.init_scale) rsp.rp.first_entry = 36 * e->n_pairs + n;
+  }
+  rsp.stamp = (lm && !final_pass) ? stamp_record(e) : nullptr;
+  return rsp;
+}
+
+int launch_reduce_and_solve(pba_engine* e, SolveParams so, int n, int cur, int cand, const LmState* lm, int final_pass, int n_cost_blocks,
+                            const ReduceSolveParams::Fin* fin = nullptr) {
+  const bool multi = e->comm.multi();
+  const int grid = reduce_grid(e);
+  const int pstride = packed_stride(n);
+  const ReduceParams rp = reduce_params(e, cur, n_cost_blocks);
   if (!multi && e->solve_kind == 0 && !(PBA_PHASE_TIMING && getenv("PBA_SPLIT_SOLVE"))) {
-    ReduceSolveParams rsp{};
-    rsp.rp = rp;
-    rsp.block_cost_alt = e->d_block_cost[cand]; rsp.block_fail_alt = e->d_block_fail[cand];
-    rsp.ticket = e->d_ticket_solve; rsp.so = so;
-    if (fin) {
-      rsp.fin = *fin;
-      // gradient-only: the pair blocks and the right-hand side of the partials are not consumed
-      if (final_pass && !so.init_scale) rsp.rp.first_entry = 36 * e->n_pairs + n;
-    }
-    rsp.stamp = (lm && !final_pass) ? stamp_record(e) : nullptr;
+    const ReduceSolveParams rsp = reduce_solve_params(e, so, n, cur, cand, lm, final_pass, n_cost_blocks, fin);
     ev_begin(e, 3);
     hipLaunchKernelGGL(k_reduce_solve, dim3(grid), dim3(kReduceThreads), solve_blocked_smem_bytes(n), e->stream, rsp);
     ev_end(e, 3);
     HIP_TRY(e, hipGetLastError());
     return PBA_OK;
   }
+  if (final_pass && !so.init_scale) { so.S_dbg = nullptr; so.rhs_dbg = nullptr; }      // (as reduce_solve_params does)
   const bool peer = multi && e->comm.peer;
   if (peer && (size_t)pstride > Comm::kCapA) return fail(e, PBA_ERR_COMM, "reduced system of %d doubles exceeds the peer mailbox", pstride);
   ReduceFinalParams fp{};
@@ -757,6 +780,8 @@ void pba_destroy(pba_engine* e) {
   dev_free(&e->d_fe_cand); dev_free(&e->d_fe_io);
   if (e->h_fe_io) (void)hipHostFree(e->h_fe_io);
   if (e->h_log) (void)hipHostFree(e->h_log);
+  if (e->h_batch) (void)hipHostFree(e->h_batch);
+  dev_free(&e->d_batch);
   dev_free(&e->d_lm);
   dev_free(&e->d_log);
   dev_free(&e->d_res_sync);
@@ -1691,8 +1716,8 @@ const char* pba_comm_transport(const pba_engine* e) {
 }
 
 const char* pba_solve_driver(const pba_engine* e) {
-  static const char* names[] = {"none", "resident", "pipelined", "host-stepped"};
-  return names[(e && e->last_driver >= 0 && e->last_driver <= 3) ? e->last_driver : 0];
+  static const char* names[] = {"none", "resident", "pipelined", "host-stepped", "batched"};
+  return names[(e && e->last_driver >= 0 && e->last_driver <= 4) ? e->last_driver : 0];
 }
 
 int pba_get_counters(pba_engine* e, pba_counters* c) {
@@ -1836,6 +1861,73 @@ int pba_internal_async_begin(pba_engine* e, const pba_solver_options* o) {
   return PBA_OK;
 }
 
+}  // extern "C"
+
+// ---- parameters of the asynchronous driver's passes (pba_internal_async_enqueue; the batched launches of pba_solve_batch use the same) ----
+namespace {
+// the fused sampling pass: kind 0 = first linearisation (plain Jacobian pass at the current point), 1 = candidate pass of a full
+// iteration (single rank: decide = 1, stamps and the sequence number are the caller's)
+SampleParams async_sample_params(pba_engine* e, int kind) {
+  const int cur = e->async_cur, cand = 1 - cur;
+  const bool skip = kind == 0;
+  unsigned long long* h_seq_dev = reinterpret_cast<unsigned long long*>(e->h_scal_dev + kNumScal);
+  SampleParams sp = make_sample_params(e, skip ? cur : cand);
+  sp.tile_info = e->d_tile_info; sp.lane_rec = e->d_lane_rec;
+  sp.geom_prev = e->d_geom[skip ? cand : cur]; sp.xyz_prev = e->d_xyz[skip ? cand : cur]; sp.rec_prev = e->d_rec[skip ? cand : cur];
+  sp.sp = e->d_sp; sp.ptrec = e->d_ptrec; sp.delta_c = e->d_delta_c; sp.block_bs = e->d_bs_out; sp.ticket = e->d_ticket;
+  sp.scal = e->d_scal; sp.n_tiles = e->n_tiles; sp.skip_backsub = skip ? 1 : 0;
+  sp.block_cost_alt = e->d_block_cost[skip ? cand : cur]; sp.block_fail_alt = e->d_block_fail[skip ? cand : cur];
+  sp.host_state = e->h_lm_dev; sp.log = e->d_log; sp.max_log = pba_engine::kMaxLog;
+  sp.host_seq = h_seq_dev; sp.enq_cur = cur;
+  sp.host_scal = nullptr;     // kind 1: published by the next k_schur (or k_flush): see SchurParams::pub_*
+  if (skip) {
+    sp.lm = nullptr; sp.seq = 0; sp.decide = 0;
+    if (!PBA_LM_INIT_KERNEL) { sp.lm_init_dst = e->d_lm; sp.lm_init_src = e->h_lm_dev; }
+  } else {
+    sp.lm = e->d_lm; sp.decide = 1;
+  }
+  return sp;
+}
+// k_schur of kind 1 (full iteration) / 2 (gradient norms of the final point); pub_seq = the engine's last sequence number, no stamps
+SchurParams async_schur_params(pba_engine* e, int kind, int init_scale, const pba_solver_options* o) {
+  const int cur = e->async_cur, cand = 1 - cur;
+  SchurParams sc{};
+  sc.xyz = e->d_xyz[cur]; sc.rays = e->inverse_depth ? e->d_rays : nullptr; sc.geom = e->d_geom[cur]; sc.rec = e->d_rec[cur]; sc.obs_point = e->d_obs_point;
+  sc.obs_slot = e->d_obs_slot; sc.tile_info = e->d_tile_info; sc.lane_rec = e->d_lane_rec; sc.sp = e->d_sp;
+  sc.ptrec = e->d_ptrec; sc.partial = e->d_partial; sc.rec_stride = e->rec_stride; sc.n_tiles = e->n_tiles; sc.n_frames = e->n_frames;
+  sc.n_free = e->n_free; sc.n_pairs = e->n_pairs; sc.part_stride = e->part_stride; sc.init_scale = init_scale;
+  // the previous enqueue decided on the device (last workgroup of the fused sampling kernel, or k_decide after the
+  // multi-rank exchange) without publishing; this kernel does
+  sc.pub_state = e->h_lm_dev; sc.pub_scal = e->d_scal; sc.pub_host_scal = e->h_scal_dev;
+  sc.pub_host_seq = reinterpret_cast<unsigned long long*>(e->h_scal_dev + kNumScal); sc.pub_seq = e->seq;
+  sc.jacobi = o->jacobi_scaling; sc.fx = e->cfg.fx; sc.fy = e->cfg.fy; sc.radius = 1.0; sc.inv_radius = 1.0;
+  sc.min_diag = o->min_lm_diagonal; sc.max_diag = o->max_lm_diagonal; sc.dbg = nullptr;
+  sc.stamp = nullptr;
+  sc.lm = e->d_lm; sc.enq_cur = cur; sc.final_pass = (kind == 2) ? 1 : 0; sc.xyz_alt = e->d_xyz[cand]; sc.geom_alt = e->d_geom[cand]; sc.rec_alt = e->d_rec[cand];
+  return sc;
+}
+SolveParams async_solve_params(pba_engine* e, int kind, int init_scale, const pba_solver_options* o) {
+  const int cur = e->async_cur, cand = 1 - cur;
+  SolveParams so{};
+  so.packed = e->d_packed; so.cams = e->d_cams[cur]; so.cams_cand = e->d_cams[cand]; so.delta_c = e->d_delta_c;
+  so.sc = e->d_sc; so.S_dbg = (e->cfg.flags & 1) ? e->d_S : nullptr; so.rhs_dbg = e->d_rhs; so.scal = e->d_scal; so.geom = e->d_geom[cur];
+  so.n_frames = e->n_frames; so.n_free = e->n_free; so.n_pairs = e->n_pairs; so.stride = e->part_stride; so.fixed_slot = e->fixed_slot; so.tab = e->d_solve_tab;
+  so.geom_cand = (kind == 1) ? e->d_geom[cand] : nullptr;
+  so.init_scale = init_scale; so.jacobi = o->jacobi_scaling; so.radius = 1.0; so.min_diag = o->min_lm_diagonal; so.max_diag = o->max_lm_diagonal;
+  so.lm = e->d_lm; so.enq_cur = cur; so.final_pass = (kind == 2) ? 1 : 0; so.cams_alt = e->d_cams[cand]; so.cams_cand_alt = e->d_cams[cur]; so.geom_alt = e->d_geom[cand];
+  so.geom_cand_alt = e->d_geom[cur];
+  return so;
+}
+// the end of a single-rank solve folded into its final pass (decision + flush by the last workgroup of k_reduce_solve)
+ReduceSolveParams::Fin async_fin(pba_engine* e, unsigned long long seq) {
+  ReduceSolveParams::Fin fin{};
+  fin.lm = e->d_lm; fin.log = e->d_log; fin.host_log = e->h_log_dev; fin.max_log = (int)pba_engine::kMaxLog; fin.host_state = e->h_lm_dev;
+  fin.host_scal = e->h_scal_dev; fin.host_seq = reinterpret_cast<unsigned long long*>(e->h_scal_dev + kNumScal); fin.seq = seq;
+  return fin;
+}
+}  // namespace
+
+extern "C" {
 // kind 0: first linearisation; 1: full iteration; 2: gradient norms of the final point; 3: flush (log + state to the
 // host).  Returns the sequence number that marks the enqueued work as complete (0 for kind 0).  Single rank: a kind-1
 // sequence number is published by the NEXT kind-1 / kind-3 enqueue, so callers end every solve with a flush.
@@ -1845,21 +1937,9 @@ int pba_internal_async_enqueue(pba_engine* e, int kind, int init_scale, const pb
   const bool multi = e->comm.multi();
   unsigned long long* h_seq_dev = reinterpret_cast<unsigned long long*>(e->h_scal_dev + kNumScal);
   *seq_out = 0;
-  auto sample_params = [&](bool skip) {
-    SampleParams sp = make_sample_params(e, skip ? cur : cand);
-    sp.tile_info = e->d_tile_info; sp.lane_rec = e->d_lane_rec;
-    sp.geom_prev = e->d_geom[skip ? cand : cur]; sp.xyz_prev = e->d_xyz[skip ? cand : cur]; sp.rec_prev = e->d_rec[skip ? cand : cur];
-    sp.sp = e->d_sp; sp.ptrec = e->d_ptrec; sp.delta_c = e->d_delta_c; sp.block_bs = e->d_bs_out; sp.ticket = e->d_ticket;
-    sp.scal = e->d_scal; sp.n_tiles = e->n_tiles; sp.skip_backsub = skip ? 1 : 0;
-    sp.block_cost_alt = e->d_block_cost[skip ? cand : cur]; sp.block_fail_alt = e->d_block_fail[skip ? cand : cur];
-    sp.host_state = e->h_lm_dev; sp.log = e->d_log; sp.max_log = pba_engine::kMaxLog;
-    return sp;
-  };
   if (kind == 0) {
     // plain Jacobian pass at the current point, on the fused (tile) grid so that both parities share one block count
-    SampleParams sp = sample_params(true);
-    sp.lm = nullptr; sp.host_scal = nullptr; sp.host_seq = h_seq_dev; sp.seq = 0; sp.decide = 0; sp.enq_cur = cur;
-    if (!PBA_LM_INIT_KERNEL) { sp.lm_init_dst = e->d_lm; sp.lm_init_src = e->h_lm_dev; }
+    SampleParams sp = async_sample_params(e, 0);
     e->stamp_iter = 0;
     sp.stamp = stamp_record(e);
     launch_sample<true, true>(e, sp);
@@ -1877,45 +1957,23 @@ int pba_internal_async_enqueue(pba_engine* e, int kind, int init_scale, const pb
     *seq_out = seq;
     return PBA_OK;
   }
-  SchurParams sc{};
-  sc.xyz = e->d_xyz[cur]; sc.rays = e->inverse_depth ? e->d_rays : nullptr; sc.geom = e->d_geom[cur]; sc.rec = e->d_rec[cur]; sc.obs_point = e->d_obs_point;
-  sc.obs_slot = e->d_obs_slot; sc.tile_info = e->d_tile_info; sc.lane_rec = e->d_lane_rec; sc.sp = e->d_sp;
-  sc.ptrec = e->d_ptrec; sc.partial = e->d_partial; sc.rec_stride = e->rec_stride; sc.n_tiles = e->n_tiles; sc.n_frames = e->n_frames;
-  sc.n_free = e->n_free; sc.n_pairs = e->n_pairs; sc.part_stride = e->part_stride; sc.init_scale = init_scale;
-  // the previous enqueue decided on the device (last workgroup of the fused sampling kernel, or k_decide after the
-  // multi-rank exchange) without publishing; this kernel does
-  sc.pub_state = e->h_lm_dev; sc.pub_scal = e->d_scal; sc.pub_host_scal = e->h_scal_dev; sc.pub_host_seq = h_seq_dev; sc.pub_seq = e->seq;
-  sc.jacobi = o->jacobi_scaling; sc.fx = e->cfg.fx; sc.fy = e->cfg.fy; sc.radius = 1.0; sc.inv_radius = 1.0;
-  sc.min_diag = o->min_lm_diagonal; sc.max_diag = o->max_lm_diagonal; sc.dbg = nullptr;
+  SchurParams sc = async_schur_params(e, kind, init_scale, o);
   if (kind == 1 && e->stamps) e->stamp_iter++;
   sc.stamp = (kind == 1) ? stamp_record(e) : nullptr;
-  sc.lm = e->d_lm; sc.enq_cur = cur; sc.final_pass = (kind == 2) ? 1 : 0; sc.xyz_alt = e->d_xyz[cand]; sc.geom_alt = e->d_geom[cand]; sc.rec_alt = e->d_rec[cand];
   launch_schur(e, sc);
-  SolveParams so{};
-  so.packed = e->d_packed; so.cams = e->d_cams[cur]; so.cams_cand = e->d_cams[cand]; so.delta_c = e->d_delta_c;
-  so.sc = e->d_sc; so.S_dbg = (e->cfg.flags & 1) ? e->d_S : nullptr; so.rhs_dbg = e->d_rhs; so.scal = e->d_scal; so.geom = e->d_geom[cur];
-  so.n_frames = e->n_frames; so.n_free = e->n_free; so.n_pairs = e->n_pairs; so.stride = e->part_stride; so.fixed_slot = e->fixed_slot; so.tab = e->d_solve_tab;
-  so.geom_cand = (kind == 1) ? e->d_geom[cand] : nullptr;
-  so.init_scale = init_scale; so.jacobi = o->jacobi_scaling; so.radius = 1.0; so.min_diag = o->min_lm_diagonal; so.max_diag = o->max_lm_diagonal;
-  so.lm = e->d_lm; so.enq_cur = cur; so.final_pass = (kind == 2) ? 1 : 0; so.cams_alt = e->d_cams[cand]; so.cams_cand_alt = e->d_cams[cur]; so.geom_alt = e->d_geom[cand];
-  so.geom_cand_alt = e->d_geom[cur];
+  SolveParams so = async_solve_params(e, kind, init_scale, o);
   // single rank: the final pass decides and flushes in its own last workgroup (no k_decide, no k_flush behind it)
   const bool fin_fused = kind == 2 && pba_internal_final_flushes(e);
   const unsigned long long seq = ++e->seq;
-  ReduceSolveParams::Fin fin{};
-  if (fin_fused) {
-    fin.lm = e->d_lm; fin.log = e->d_log; fin.host_log = e->h_log_dev; fin.max_log = (int)pba_engine::kMaxLog; fin.host_state = e->h_lm_dev;
-    fin.host_scal = e->h_scal_dev; fin.host_seq = h_seq_dev; fin.seq = seq;
-  }
+  const ReduceSolveParams::Fin fin = async_fin(e, seq);
   { const int rcs = launch_reduce_and_solve(e, so, n, cur, cand, e->d_lm, kind == 2 ? 1 : 0, e->fused_grid, fin_fused ? &fin : nullptr); if (rcs) return rcs; }
   if (fin_fused) { HIP_TRY(e, hipGetLastError()); *seq_out = seq; return PBA_OK; }
   unsigned long long fused_x = 0;      // exchange number of the step scalars when k_decide does the exchange itself
   if (kind == 1) {
-    SampleParams sp = sample_params(false);
-    sp.lm = e->d_lm; sp.enq_cur = cur; sp.decide = multi ? 0 : 1;
+    SampleParams sp = async_sample_params(e, 1);
+    sp.decide = multi ? 0 : 1;
     sp.stamp = stamp_record(e);
-    sp.host_scal = nullptr;     // published by the next k_schur (or k_flush): see SchurParams::pub_*
-    sp.host_seq = h_seq_dev; sp.seq = seq;
+    sp.seq = seq;
     if (multi) {
       int rcx = ensure_xchg(e);
       if (rcx) return rcx;
@@ -2180,5 +2238,181 @@ void pba_internal_reset_pass_counts(pba_engine* e) { e->jac_passes = 0; e->cost_
 int pba_internal_allreduce_host(pba_engine* e, double* v, int n, int op) {
   if (!e->comm.multi()) return 0;
   return e->comm.allreduce_host(v, n, op);
+}
+}  // extern "C"
+
+// ---- batched solves (pba_solve_batch: pba_lm.cpp drives, pba_batch.h computes) ------------------------------------------
+namespace {
+int batch_refuse(pba_engine* const* es, int i, int code, const char* fmt, ...) {
+  char buf[400];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  if (es[0]) fail(es[0], code, "pba_solve_batch: engine %d: %s", i, buf);
+  if (i >= 0 && es[i]) fail(es[i], code, "pba_solve_batch: engine %d: %s", i, buf);
+  return code;
+}
+
+template <int R>
+void launch_sample_batch_r(const pba_engine* e0, int grid, const BatchLaunch& L, hipStream_t st) {
+  const dim3 block(kSampleWaves * 64);
+  if (e0->channels > 1) {
+    if (e0->unit_weights) hipLaunchKernelGGL((k_sample_mc_batch<R, true>), dim3(grid), block, 0, st, L);
+    else hipLaunchKernelGGL((k_sample_mc_batch<R, false>), dim3(grid), block, 0, st, L);
+  } else {
+    if (e0->unit_weights) hipLaunchKernelGGL((k_sample_batch<R, true>), dim3(grid), block, 0, st, L);
+    else hipLaunchKernelGGL((k_sample_batch<R, false>), dim3(grid), block, 0, st, L);
+  }
+}
+void launch_sample_batch(const pba_engine* e0, int grid, const BatchLaunch& L, hipStream_t st) {
+  switch (e0->cfg.radius) {
+    case 1: launch_sample_batch_r<1>(e0, grid, L, st); break;
+    case 2: launch_sample_batch_r<2>(e0, grid, L, st); break;
+    case 3: launch_sample_batch_r<3>(e0, grid, L, st); break;
+    case 4: launch_sample_batch_r<4>(e0, grid, L, st); break;
+    default: launch_sample_batch_r<5>(e0, grid, L, st); break;
+  }
+}
+}  // namespace
+
+extern "C" {
+// Every condition of pba_solve_batch (include/pba.h), checked before anything touches a device.
+int pba_internal_batch_validate(pba_engine* const* es, int32_t n, const pba_solver_options* o) {
+  if (!es || n < 1 || n > PBA_MAX_BATCH) return PBA_ERR_INVALID;
+  for (int i = 0; i < n; ++i) if (!es[i]) return batch_refuse(es, i, PBA_ERR_INVALID, "the engine is null");
+  const pba_engine* e0 = es[0];
+  for (int i = 0; i < n; ++i) {
+    pba_engine* e = es[i];
+    for (int j = 0; j < i; ++j)
+      if (es[j] == e) return batch_refuse(es, i, PBA_ERR_INVALID, "the same engine as index %d (every window appears once)", j);
+    if (e->cfg.device != e0->cfg.device) return batch_refuse(es, i, PBA_ERR_INVALID, "on device %d, the batch is on device %d", e->cfg.device, e0->cfg.device);
+    if (e->poisoned) return batch_refuse(es, i, PBA_ERR_STATE, "the engine is unusable after a timed-out step; destroy it");
+    if (check_ready(e, "pba_solve_batch")) return batch_refuse(es, i, PBA_ERR_STATE, "%s", e->err.c_str());
+    if (e->comm.kind != 0 || e->comm.multi()) return batch_refuse(es, i, PBA_ERR_INVALID, "multi-rank engines (pba_comm_*) solve alone");
+    if (e->wide || e->n_free > kMaxFrames - 1) return batch_refuse(es, i, PBA_ERR_INVALID, "wide window (%d free cameras, a batch takes <= %d)", e->n_free, kMaxFrames - 1);
+    if ((e->cfg.flags >> 1) & 3) return batch_refuse(es, i, PBA_ERR_INVALID, "the precision-sweep flags solve alone");
+    if (e->profile || e->stamps) return batch_refuse(es, i, PBA_ERR_INVALID, "profiling is on (pba_set_profiling / pba_reset_counters)");
+    if (!pba_internal_async_capable(e, &o[i]) || e->solve_kind != 0)
+      return batch_refuse(es, i, PBA_ERR_INVALID, "the options or the environment need the host-stepped driver (max_num_iterations %d)", o[i].max_num_iterations);
+    if (e->cfg.radius != e0->cfg.radius) return batch_refuse(es, i, PBA_ERR_INVALID, "patch radius %d, engine 0 has %d (one kernel key per batch)", e->cfg.radius, e0->cfg.radius);
+    if (e->channels != e0->channels) return batch_refuse(es, i, PBA_ERR_INVALID, "%d channels, engine 0 has %d (one kernel key per batch)", e->channels, e0->channels);
+    if (e->unit_weights != e0->unit_weights)
+      return batch_refuse(es, i, PBA_ERR_INVALID, "%s patch weights, engine 0 has %s (one kernel key per batch)", e->unit_weights ? "unit" : "Gaussian", e0->unit_weights ? "unit" : "Gaussian");
+    if (e->n_tiles < 1 || e->n_free < 1) return batch_refuse(es, i, PBA_ERR_INVALID, "empty window (%d observations, %d free cameras)", e->n_obs, e->n_free);
+    if ((double)e->n_obs * pba_internal_patch_len(e) > 2147483647.0)
+      return batch_refuse(es, i, PBA_ERR_INVALID, "%d residual blocks x %d residuals exceed the int32 range of the summary", e->n_obs, pba_internal_patch_len(e));
+  }
+  return PBA_OK;
+}
+
+// Orders every engine's own stream in front of the batch stream (engine 0's), lends that stream to every engine, begins every window's
+// solve (pba_internal_async_begin) and uploads the window table.
+int pba_internal_batch_begin(pba_engine* const* es, int32_t n, const pba_solver_options* o) {
+  pba_engine* e0 = es[0];
+  HIP_TRY(e0, hipSetDevice(e0->cfg.device));
+  hipStream_t bs = e0->stream;
+  for (int i = 1; i < n; ++i) {
+    HIP_TRY(e0, hipEventRecord(es[i]->ev_xdep, es[i]->stream));
+    HIP_TRY(e0, hipStreamWaitEvent(bs, es[i]->ev_xdep, 0));
+  }
+  for (int i = 0; i < n; ++i) { es[i]->stream_own = es[i]->stream; es[i]->stream = bs; }
+  if (e0->batch_cap < n) {
+    if (e0->h_batch) { (void)hipHostFree(e0->h_batch); e0->h_batch = nullptr; }
+    e0->batch_cap = 0;
+    HIP_TRY(e0, hipHostMalloc(reinterpret_cast<void**>(&e0->h_batch), sizeof(BatchWindow) * PBA_MAX_BATCH, hipHostMallocDefault));
+    const int rc = dev_alloc(e0, &e0->d_batch, (size_t)PBA_MAX_BATCH);
+    if (rc) return rc;
+    e0->batch_cap = PBA_MAX_BATCH;
+  }
+  for (int i = 0; i < n; ++i) {
+    pba_engine* e = es[i];
+    const int rc = pba_internal_async_begin(e, &o[i]);
+    if (rc) return batch_refuse(es, i, rc, "%s", e->err.c_str());
+    const int cur = e->async_cur, cand = 1 - cur, nn = 6 * e->n_free;
+    e->batch_init2 = o[i].max_num_iterations <= 0 ? 1 : 0;
+    BatchWindow& bw = e0->h_batch[i];
+    bw = BatchWindow{};
+    bw.sample[0] = async_sample_params(e, 0);
+    bw.sample[1] = async_sample_params(e, 1);
+    bw.schur[0] = async_schur_params(e, 1, 0, &o[i]);
+    bw.schur[1] = async_schur_params(e, 2, e->batch_init2, &o[i]);
+    bw.rsolve[0] = reduce_solve_params(e, async_solve_params(e, 1, 0, &o[i]), nn, cur, cand, e->d_lm, 0, e->fused_grid, nullptr);
+    const ReduceSolveParams::Fin fin = async_fin(e, 0);      // (the sequence number travels with the launch)
+    bw.rsolve[1] = reduce_solve_params(e, async_solve_params(e, 2, e->batch_init2, &o[i]), nn, cur, cand, e->d_lm, 1, e->fused_grid, &fin);
+    bw.frames_mc = e->channels > 1 ? e->d_frames_mc : nullptr;
+    bw.channels = e->channels;
+  }
+  HIP_TRY(e0, hipMemcpyAsync(e0->d_batch, e0->h_batch, sizeof(BatchWindow) * n, hipMemcpyHostToDevice, bs));
+  return PBA_OK;
+}
+
+// One batched pass of `kind` (0: first linearisation; 1: full iteration; 2: the final gradient-only pass, which decides and flushes) over
+// the windows sel[0..n_sel) -- indices into es -- in one launch per phase.  seq_out[k]: the sequence number of window sel[k]'s enqueue.
+int pba_internal_batch_enqueue(pba_engine* const* es, const int32_t* sel, int32_t n_sel, int kind, int init_scale, unsigned long long* seq_out) {
+  pba_engine* e0 = es[0];
+  if (n_sel < 1) return PBA_OK;
+  hipStream_t bs = e0->stream;
+  BatchLaunch L{};
+  L.tab = e0->d_batch;
+  L.n = n_sel;
+  int g_schur = 0, g_red = 0, g_sample = 0;
+  size_t lds = 0;
+  for (int k = 0; k < n_sel; ++k) {
+    pba_engine* e = es[sel[k]];
+    L.win[k] = (uint8_t)sel[k];
+    const int init = kind == 2 ? e->batch_init2 : init_scale;
+    L.mode[k] = (uint8_t)((kind == 2 ? 1 : 0) | (init ? 2 : 0));
+    if (kind == 0) { seq_out[k] = 0; e->jac_passes++; e->cost_blocks[0] = e->cost_blocks[1] = e->fused_grid; }
+    else { L.seq[k] = seq_out[k] = ++e->seq; if (kind == 1) e->jac_passes++; }
+    lds = std::max(lds, solve_blocked_smem_bytes(6 * e->n_free));
+  }
+  auto grids = [&](auto grid_of) {
+    int g = 0;
+    for (int k = 0; k < n_sel; ++k) { L.begin[k] = g; g += grid_of(es[sel[k]]); }
+    L.begin[n_sel] = g;
+    return g;
+  };
+  if (kind != 0) {
+    g_schur = grids([](const pba_engine* e) { return e->schur_grid; });
+    hipLaunchKernelGGL(k_schur_batch, dim3(g_schur), dim3(kTile), 0, bs, L);
+    g_red = grids([](const pba_engine* e) { return reduce_grid(e); });
+    hipLaunchKernelGGL(k_reduce_solve_batch, dim3(g_red), dim3(kReduceThreads), lds, bs, L);
+  }
+  if (kind != 2) {
+    if (kind == 1) for (int k = 0; k < n_sel; ++k) L.mode[k] = 1;     // sampling variant 1: the candidate pass
+    g_sample = grids([](const pba_engine* e) { return e->fused_grid; });
+    launch_sample_batch(e0, g_sample, L, bs);
+  }
+  HIP_TRY(e0, hipGetLastError());
+  return PBA_OK;
+}
+
+// Gives every engine its own stream back, ordered behind the batch; after a timed-out wait (one engine poisoned) every engine of the batch
+// is poisoned: they all share the stalled stream.
+void pba_internal_batch_end(pba_engine* const* es, int32_t n, int failed) {
+  pba_engine* e0 = es[0];
+  int bad = -1;
+  for (int i = 0; i < n; ++i) if (es[i]->poisoned) bad = i;
+  for (int i = 0; i < n; ++i) {
+    if (es[i]->stream_own) es[i]->stream = es[i]->stream_own;
+    es[i]->stream_own = nullptr;
+  }
+  if (bad >= 0) {
+    for (int i = 0; i < n; ++i) {
+      if (!es[i]->poisoned) {
+        es[i]->poisoned = true;
+        es[i]->err = "pba_solve_batch: a wait of engine " + std::to_string(bad) + " of the batch timed out; the engine is unusable, destroy it";
+      }
+    }
+    return;
+  }
+  // (a batch that failed part-way drains the stream: the pinned table staging may still be read by its copy)
+  if (failed) (void)hipStreamSynchronize(e0->stream);
+  (void)hipEventRecord(e0->ev_xdep, e0->stream);
+  for (int i = 0; i < n; ++i) {
+    if (i > 0) (void)hipStreamWaitEvent(es[i]->stream, e0->ev_xdep, 0);
+    if (!failed) es[i]->last_driver = 4;
+  }
 }
 }  // extern "C"

@@ -35,4 +35,10 @@ void pba_internal_resident_done(pba_engine* e, int iterations);   /* the solve t
 void pba_internal_resident_failed(pba_engine* e);   /* a resident launch ended without publishing (device-side wait timed out): the engine is unusable */
 void pba_internal_resident_trace(pba_engine* e, int iterations);   /* PBA_RES_TRACE: phase intervals of the last resident solve to stderr */
 int pba_internal_final_flushes(const pba_engine* e);   /* 1: the kind-2 enqueue also flushes (no kind 3 behind it) */
+// batched solves (pba_solve_batch, pba_batch.h): validate (nothing touches a device), begin (streams ordered and lent, every window begun,
+// the window table uploaded), one batched pass of kind 0 | 1 | 2 over the windows sel[] (indices into es), end (streams given back)
+int pba_internal_batch_validate(pba_engine* const* es, int32_t n, const pba_solver_options* o);
+int pba_internal_batch_begin(pba_engine* const* es, int32_t n, const pba_solver_options* o);
+int pba_internal_batch_enqueue(pba_engine* const* es, const int32_t* sel, int32_t n_sel, int kind, int init_scale, unsigned long long* seq_out);
+void pba_internal_batch_end(pba_engine* const* es, int32_t n, int failed);
 }

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <vector>
 
 #include "../../include/pba.h"
 
@@ -352,5 +353,90 @@ extern "C" int pba_solve(pba_engine* e, const pba_solver_options* o, pba_solver_
   sum->final_cost = minimum_cost;
   sum->num_iterations = n_it < max_out ? n_it : max_out;
   sum->total_time_in_seconds = now() - t_start;
+  return PBA_OK;
+}
+
+// Batch variant of solve_async: n independent windows, one batched launch per phase on ONE stream (pba_batch.h).  Each window follows the
+// loop of solve_async step for step -- the same enqueue / wait rule per window, the same final pass through lm_final_pass_needed, the
+// same summary -- and all windows still running advance together, so window w's k-th full iteration is in the batch's k-th launch.
+extern "C" int pba_solve_batch(pba_engine* const* es, int32_t n, const pba_solver_options* options, pba_solver_summary* sums,
+                               pba_iteration_summary* its, int32_t max_out) {
+  constexpr int kAhead = 3;     // solve_async's
+  if (!es || !sums || n < 1 || n > PBA_MAX_BATCH || (its && max_out < 0)) return PBA_ERR_INVALID;
+  std::vector<pba_solver_options> o((size_t)n);
+  for (int w = 0; w < n; ++w) {
+    if (options) o[w] = options[w];
+    else pba_default_solver_options(&o[w]);
+  }
+  { const int rc = pba_internal_batch_validate(es, n, o.data()); if (rc) return rc; }
+  const double t_start = now();
+  for (int w = 0; w < n; ++w) {
+    pba_solver_summary* sum = &sums[w];
+    std::memset(sum, 0, sizeof(*sum));
+    sum->termination_type = 1;
+    std::snprintf(sum->message, sizeof(sum->message), "Maximum number of iterations reached.");
+    sum->num_residual_blocks = (int32_t)pba_internal_local_blocks(es[w]);
+    sum->num_residuals = (int32_t)(pba_internal_local_blocks(es[w]) * pba_internal_patch_len(es[w]));
+    sum->fixed_cost = 0.0;
+    pba_internal_reset_pass_counts(es[w]);
+  }
+  int rc = pba_internal_batch_begin(es, n, o.data());
+  enum { kRunning, kFinished };
+  std::vector<int> phase((size_t)n, kRunning), enq((size_t)n, 0);
+  std::vector<unsigned long long> final_seq((size_t)n, 0), ring((size_t)n * (kAhead + 1), 0), seq_k((size_t)n, 0);
+  std::vector<int32_t> sel, fin;
+  sel.reserve(n); fin.reserve(n);
+  for (int w = 0; w < n && !rc; ++w) sel.push_back(w);
+  if (!rc) rc = pba_internal_batch_enqueue(es, sel.data(), (int32_t)sel.size(), 0, 0, seq_k.data());
+  for (int j = 0; !rc; ++j) {
+    sel.clear(); fin.clear();
+    for (int w = 0; w < n; ++w) {
+      if (phase[w] != kRunning) continue;
+      const volatile pba::LmState* st = static_cast<const volatile pba::LmState*>(pba_internal_async_state(es[w]));
+      if (enq[w] >= o[w].max_num_iterations) { phase[w] = kFinished; fin.push_back(w); continue; }   // the iteration limit: final pass
+      if (st->done) {             // terminated: the flush alone (kind 3)
+        phase[w] = kFinished;
+        if ((rc = pba_internal_async_enqueue(es[w], 3, 0, &o[w], &final_seq[w]))) break;
+        continue;
+      }
+      sel.push_back(w);
+    }
+    if (rc) break;
+    if (!fin.empty()) {
+      // gradient norms of the final point, gated on the device (lm_final_pass_needed); single rank, it decides and flushes itself
+      std::vector<int32_t> fused;
+      for (int32_t w : fin) {
+        if (pba_internal_final_flushes(es[w])) { fused.push_back(w); continue; }
+        unsigned long long s2 = 0;
+        if ((rc = pba_internal_async_enqueue(es[w], 2, o[w].max_num_iterations <= 0 ? 1 : 0, &o[w], &s2))) break;
+        if ((rc = pba_internal_async_enqueue(es[w], 3, 0, &o[w], &final_seq[w]))) break;
+      }
+      if (rc) break;
+      if (!fused.empty()) {
+        if ((rc = pba_internal_batch_enqueue(es, fused.data(), (int32_t)fused.size(), 2, 0, seq_k.data()))) break;
+        for (size_t k = 0; k < fused.size(); ++k) final_seq[fused[k]] = seq_k[k];
+      }
+    }
+    if (sel.empty()) break;
+    if ((rc = pba_internal_batch_enqueue(es, sel.data(), (int32_t)sel.size(), 1, j == 0 ? 1 : 0, seq_k.data()))) break;
+    for (size_t k = 0; k < sel.size() && !rc; ++k) {
+      const int w = sel[k];
+      unsigned long long* seqs = &ring[(size_t)w * (kAhead + 1)];
+      seqs[enq[w] % (kAhead + 1)] = seq_k[k];
+      ++enq[w];
+      if (enq[w] > kAhead) rc = pba_internal_async_wait(es[w], seqs[(enq[w] - kAhead) % (kAhead + 1)]);
+    }
+  }
+  for (int w = 0; w < n && !rc; ++w) {
+    if ((rc = pba_internal_async_wait(es[w], final_seq[w]))) break;
+    rc = pba_internal_async_end(es[w]);
+  }
+  pba_internal_batch_end(es, n, rc != 0);
+  if (rc) return rc;
+  for (int w = 0; w < n; ++w) {
+    const bool verbose = o[w].verbose != 0;
+    const int rcw = summarize_device_solve(es[w], &o[w], &sums[w], its ? its + (size_t)w * (size_t)max_out : nullptr, its ? max_out : 0, t_start, verbose, -1);
+    if (rcw) return rcw;
+  }
   return PBA_OK;
 }

@@ -324,3 +324,40 @@ class Engine:
         c = _lib.Counters()
         self._check(self._L.pba_get_counters(self._h, C.byref(c)), "pba_get_counters")
         return {f: getattr(c, f) for f, _ in _lib.Counters._fields_}
+
+
+def solve_batch(engines, options=None, max_iterations_out=512, fetch_state=True):
+    """pba_solve_batch: solves independent windows together, one batched launch per phase of every LM iteration; returns one dict per
+    engine in the shape of Engine.solve, each equal to that engine's own solve.  `options`: None, one options object for all, or a list."""
+    engines = list(engines)
+    n = len(engines)
+    if n < 1 or n > _lib.MAX_BATCH:
+        raise EngineError("solve_batch: %d engines (1 to %d)" % (n, _lib.MAX_BATCH))
+    if options is None:
+        opts = [default_solver_options() for _ in range(n)]
+    elif isinstance(options, _lib.SolverOptions):
+        opts = [options] * n
+    else:
+        opts = list(options)
+        if len(opts) != n:
+            raise EngineError("solve_batch: %d option sets for %d engines" % (len(opts), n))
+    L = _lib.lib()
+    handles = (C.c_void_p * n)(*[e._h for e in engines])
+    o_arr = (_lib.SolverOptions * n)(*opts)
+    sums = (_lib.SolverSummary * n)()
+    m = int(max_iterations_out)
+    its = (_lib.IterationSummary * (n * m))()
+    rc = L.pba_solve_batch(handles, n, o_arr, sums, its, m)
+    if rc != 0:
+        raise EngineError("pba_solve_batch: %s (%s)" % (L.pba_status_string(rc).decode(),
+                                                         L.pba_last_error(engines[0]._h).decode() if engines[0]._h else ""))
+    out = []
+    for w, e in enumerate(engines):
+        s = sums[w]
+        res = {f: getattr(s, f) for f, _ in _lib.SolverSummary._fields_}
+        res["message"] = s.message.decode()
+        res["iterations"] = [{f: getattr(its[w * m + i], f) for f, _ in _lib.IterationSummary._fields_} for i in range(s.num_iterations)]
+        if fetch_state:
+            res["cams"], res["xyz"] = e.get_state()
+        out.append(res)
+    return out

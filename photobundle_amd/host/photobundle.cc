@@ -287,6 +287,10 @@ double wall_ms() {
 }  // namespace
 
 void PhotometricBundleAdjustment::addFrame(const uint8_t* I_ptr, const float* Z_ptr, const Mat44& T, Result* result) {
+  (void)addFrameImpl(I_ptr, Z_ptr, T, result, false);
+}
+
+bool PhotometricBundleAdjustment::addFrameImpl(const uint8_t* I_ptr, const float* Z_ptr, const Mat44& T, Result* result, bool defer) {
   const double t_enter = wall_ms();
   _trajectory.push_back(T, _frame_id);
   const Mat44 T_w = _trajectory.back();
@@ -528,31 +532,56 @@ void PhotometricBundleAdjustment::addFrame(const uint8_t* I_ptr, const float* Z_
   _frame_buffer.push_back(std::move(frame));
   lap(4);
   const double t_front = wall_ms();
-  if ((int)_frame_buffer.size() == window) optimize(result);
+  const bool due = (int)_frame_buffer.size() == window;
+  if (due && !defer) optimize(result);
   if (_options_ptr->verbose)
     std::fprintf(stderr, "addFrame %.2f ms (front-end %.2f ms, optimize %.2f ms)  [frame+upload %.2f, visibility %.2f, saliency %.2f, "
                  "candidates %.2f, top-N+descriptors %.2f]  (float plane %.2f, visibility parallel part %.2f of %d points, %d tried)\n", wall_ms() - t_enter, t_front - t_enter, wall_ms() - t_front,
                  t_ph[0] + t_ph[5], t_ph[1], t_ph[2], t_ph[3], t_ph[4], t_ph[5], t_vis_par, n_vis, max_num_to_update);
   ++_frame_id;
+  return due;
 }
 
-void PhotometricBundleAdjustment::optimize(Result* result) {
+// what optimize() carries from the assembly to the read-back (one per instance: addFrames holds several at once)
+struct PhotometricBundleAdjustment::OptimizeState {
   double t_o[6] = {0, 0, 0, 0, 0, 0};
-  double t_lo = wall_ms();
-  auto lap_o = [&](int k) { const double t = wall_ms(); t_o[k] += t - t_lo; t_lo = t; };
+  double t_lo = 0.0;
+  uint32_t frame_id_start = 0, frame_id_end = 0;
+  std::vector<double> cams, xyz;
+  std::vector<ScenePoint*> selected;
+  pba_solver_options so;
+  pba_solver_summary summary;
+  std::vector<pba_iteration_summary> its;
+  void lap(int k) { const double t = wall_ms(); t_o[k] += t - t_lo; t_lo = t; }
+};
+
+void PhotometricBundleAdjustment::optimize(Result* result) {
+  OptimizeState st;
+  if (optimizeAssemble(st)) {
+    check(_engine, pba_solve(_engine, &st.so, &st.summary, st.its.data(), (int32_t)st.its.size()), "pba_solve");
+    st.lap(3);
+  }
+  optimizeFinish(st, result);
+}
+
+bool PhotometricBundleAdjustment::optimizeAssemble(OptimizeState& st) {
+  st.t_lo = wall_ms();
   const uint32_t frame_id_start = _frame_buffer.front()->id, frame_id_end = _frame_buffer.back()->id;
+  st.frame_id_start = frame_id_start; st.frame_id_end = frame_id_end;
   const int window = _options_ptr->slidingWindowSize;
   const std::vector<double> patch_weights = MakePatchWeights(_options_ptr->patchRadius, _options_ptr->doGaussianWeighting);
   const int P = (int)patch_weights.size() * (int)_frame_buffer.front()->numChannels();   // descriptor entries per point
 
   // cameras: INVERTED world poses as angle-axis + t (reference :774-778), stored by ring slot id % window
-  std::vector<double> cams(6 * (size_t)window, 0.0);
+  std::vector<double>& cams = st.cams;
+  cams.assign(6 * (size_t)window, 0.0);
   for (uint32_t id = frame_id_start; id <= frame_id_end; ++id)
     PoseToParams(_trajectory.atId((int)id).inverse(), &cams[6 * (id % window)]);
 
   // points with >= 3 observations whose reference frame is inside the window; one block per visible frame (:786-806)
-  std::vector<ScenePoint*> selected;
-  std::vector<double> xyz, desc;
+  std::vector<ScenePoint*>& selected = st.selected;
+  std::vector<double>& xyz = st.xyz;
+  std::vector<double> desc;
   std::vector<int32_t> obs_point, obs_slot;
   selected.reserve(_scene_points.size());
   xyz.reserve(3 * _scene_points.size());
@@ -602,14 +631,13 @@ void PhotometricBundleAdjustment::optimize(Result* result) {
     }
   }
 
-  lap_o(0);
-  pba_solver_summary summary;
-  std::memset(&summary, 0, sizeof(summary));
-  std::vector<pba_iteration_summary> its(512);
+  st.lap(0);
+  std::memset(&st.summary, 0, sizeof(st.summary));
+  st.its.assign(512, pba_iteration_summary{});
   if (!selected.empty()) {
     check(_engine, pba_set_problem(_engine, (int32_t)selected.size(), xyz.data(), desc.data(), (int32_t)obs_point.size(),
                                   obs_point.data(), obs_slot.data(), patch_weights.data()), "pba_set_problem");
-    lap_o(1);
+    st.lap(1);
     // "set the first camera constant" only if it is part of the problem (reference :809-815, HasParameterBlock).  When it
     // is not, the reference only warns: no camera is constant and the first one is not a parameter block of the program.
     // The engine gets the first slot as its constant slot in BOTH cases: a constant camera without residual blocks is the
@@ -620,12 +648,28 @@ void PhotometricBundleAdjustment::optimize(Result* result) {
     const bool first_in_bundle = std::find(obs_slot.begin(), obs_slot.end(), first_slot) != obs_slot.end();
     if (!first_in_bundle) std::fprintf(stderr, "first camera is not in bundle\n");
     check(_engine, pba_set_cameras(_engine, cams.data(), window, first_slot), "pba_set_cameras");
-    lap_o(2);
-    pba_solver_options so;
-    pba_default_solver_options(&so);     // GetSolverOptions (:738-761)
-    so.verbose = _options_ptr->verbose ? 1 : 0;
-    check(_engine, pba_solve(_engine, &so, &summary, its.data(), (int32_t)its.size()), "pba_solve");
-    lap_o(3);
+    st.lap(2);
+    pba_default_solver_options(&st.so);     // GetSolverOptions (:738-761)
+    st.so.verbose = _options_ptr->verbose ? 1 : 0;
+    return true;
+  }
+  std::fprintf(stderr, "first camera is not in bundle\n");   // empty problem: ceres::Solve would return at once
+  (void)P;
+  return false;
+}
+
+// after the solve (or an empty problem): refined state back into the class, eviction, Result
+void PhotometricBundleAdjustment::optimizeFinish(OptimizeState& st, Result* result) {
+  const uint32_t frame_id_start = st.frame_id_start, frame_id_end = st.frame_id_end;
+  const int window = _options_ptr->slidingWindowSize;
+  const pba_solver_summary& summary = st.summary;
+  const std::vector<pba_iteration_summary>& its = st.its;
+  std::vector<double>& cams = st.cams;
+  std::vector<double>& xyz = st.xyz;
+  const std::vector<ScenePoint*>& selected = st.selected;
+  double* t_o = st.t_o;
+  auto lap_o = [&](int k) { st.lap(k); };
+  if (!selected.empty()) {
     if (_options_ptr->verbose)
       std::printf("pba_solve: %s  initial %.6e  final %.6e  iterations %d (successful %d)  %.3f s\n", summary.message,
                   summary.initial_cost, summary.final_cost, summary.num_iterations, summary.num_successful_steps,
@@ -635,10 +679,7 @@ void PhotometricBundleAdjustment::optimize(Result* result) {
     // put back the refined camera poses (:841-844)
     for (uint32_t id = frame_id_start; id <= frame_id_end; ++id)
       _trajectory.atId((int)id) = ParamsToPose(&cams[6 * (id % window)]).inverse();
-  } else {
-    std::fprintf(stderr, "first camera is not in bundle\n");   // empty problem: ceres::Solve would return at once
   }
-  (void)P;
 
   lap_o(4);
   auto points_to_remove = removePointsAtFrame(frame_id_start);
@@ -675,6 +716,65 @@ void PhotometricBundleAdjustment::optimize(Result* result) {
       result->iterationSummary.push_back(o);
     }
   }
+}
+
+void PhotometricBundleAdjustment::addFrames(const std::vector<PhotometricBundleAdjustment*>& instances, const std::vector<Frame>& frames,
+                                            const std::vector<Result*>& results) {
+  const size_t n = instances.size();
+  if (frames.size() != n || (!results.empty() && results.size() != n)) throw std::invalid_argument("addFrames: one frame (and result) per instance");
+  for (size_t i = 0; i < n; ++i) {
+    if (!instances[i] || !frames[i].T) throw std::invalid_argument("addFrames: null instance or pose");
+    for (size_t j = 0; j < i; ++j) if (instances[j] == instances[i]) throw std::invalid_argument("addFrames: an instance appears twice");
+  }
+  auto result_of = [&](size_t i) { return results.empty() ? nullptr : results[i]; };
+  std::vector<size_t> due;
+  for (size_t i = 0; i < n; ++i)
+    if (instances[i]->addFrameImpl(frames[i].image, frames[i].depth_map, *frames[i].T, result_of(i), true)) due.push_back(i);
+  std::vector<OptimizeState> st(due.size());
+  std::vector<size_t> solve;      // indices into due / st of the windows with a problem
+  for (size_t k = 0; k < due.size(); ++k) if (instances[due[k]]->optimizeAssemble(st[k])) solve.push_back(k);
+  // one batch per kernel key (and device), PBA_MAX_BATCH windows at most
+  std::vector<bool> done(solve.size(), false);
+  for (size_t a = 0; a < solve.size(); ++a) {
+    if (done[a]) continue;
+    const Options& oa = *instances[due[solve[a]]]->_options_ptr;
+    std::vector<size_t> group;
+    for (size_t b = a; b < solve.size() && (int)group.size() < PBA_MAX_BATCH; ++b) {
+      const Options& ob = *instances[due[solve[b]]]->_options_ptr;
+      if (done[b] || ob.patchRadius != oa.patchRadius || ob.descriptorType != oa.descriptorType || ob.doGaussianWeighting != oa.doGaussianWeighting ||
+          ob.device != oa.device)
+        continue;
+      group.push_back(solve[b]);
+      done[b] = true;
+    }
+    std::vector<pba_engine*> es;
+    std::vector<pba_solver_options> so;
+    for (size_t k : group) { es.push_back(instances[due[k]]->_engine); so.push_back(st[k].so); }
+    // every window shares one iteration-log length (OptimizeState::its)
+    const int32_t m = (int32_t)st[group[0]].its.size();
+    std::vector<pba_solver_summary> sums(group.size());
+    std::vector<pba_iteration_summary> its((size_t)m * group.size());
+    const double t0 = wall_ms();
+    const int rc = pba_solve_batch(es.data(), (int32_t)es.size(), so.data(), sums.data(), its.data(), m);
+    if (rc == PBA_ERR_INVALID) {      // refused before anything ran (a wide window, say): each solves alone
+      for (size_t k : group) {
+        PhotometricBundleAdjustment* pb = instances[due[k]];
+        check(pb->_engine, pba_solve(pb->_engine, &st[k].so, &st[k].summary, st[k].its.data(), (int32_t)st[k].its.size()), "pba_solve");
+        st[k].lap(3);
+      }
+      continue;
+    }
+    check(es[0], rc, "pba_solve_batch");
+    const double dt = wall_ms() - t0;
+    for (size_t g = 0; g < group.size(); ++g) {
+      OptimizeState& s = st[group[g]];
+      s.summary = sums[g];
+      std::copy(its.begin() + (ptrdiff_t)g * m, its.begin() + (ptrdiff_t)(g + 1) * m, s.its.begin());
+      s.t_o[3] += dt;
+      s.t_lo = wall_ms();
+    }
+  }
+  for (size_t k = 0; k < due.size(); ++k) instances[due[k]]->optimizeFinish(st[k], result_of(due[k]));
 }
 
 const PhotometricBundleAdjustment::DescriptorFrame* PhotometricBundleAdjustment::getFrameAtId(uint32_t id) const {

@@ -70,6 +70,14 @@ class PhotometricBundleAdjustment {
   // an optimisation ran, i.e. once the sliding window is full.
   void addFrame(const uint8_t* image, const float* depth_map, const Mat44& T, Result* result = nullptr);
 
+  // Several independent sequences in lockstep (new): addFrame's front-end for every instance, then ONE pba_solve_batch per kernel key
+  // (patch radius, descriptor channels, Gaussian weighting) over every instance whose window is full, then each instance's read-back,
+  // eviction and Result.  Each instance ends exactly where its own addFrame would.  frames[i] / results[i] (results may be empty or hold
+  // nulls) belong to instances[i]; instances appear once each.  A group the batch refuses is solved instance by instance.
+  struct Frame { const uint8_t* image; const float* depth_map; const Mat44* T; };
+  static void addFrames(const std::vector<PhotometricBundleAdjustment*>& instances, const std::vector<Frame>& frames,
+                        const std::vector<Result*>& results);
+
   // ---- solver / front-end settings: field names, meanings and ConfigFile keys of the reference ----
   struct Options {
     // front-end
@@ -132,6 +140,12 @@ class PhotometricBundleAdjustment {
  private:
   struct ScenePoint;
   struct DescriptorFrame;
+  struct OptimizeState;
+  // addFrame in parts (addFrames runs them over several instances): the front-end returns whether an optimisation is due and, with
+  // `defer`, leaves it to the caller; optimize = assemble (problem + cameras into the engine; false: nothing to solve), solve, finish
+  bool addFrameImpl(const uint8_t* image, const float* depth_map, const Mat44& T, Result* result, bool defer);
+  bool optimizeAssemble(OptimizeState& st);
+  void optimizeFinish(OptimizeState& st, Result* result);
   typedef UniquePointer<ScenePoint> ScenePointPointer;
   typedef std::vector<ScenePointPointer> ScenePointPointerList;
 
