@@ -284,18 +284,28 @@ def block_system(p, bp, radius, scale, dt):
     sc, sp = scale
     Hcc, gc = Hcc * sc[:, :, None] * sc[:, None, :], gc * sc
     Hpp, gp = Hpp * sp[:, :, None] * sp[:, None, :], gp * sp
+    damp = []
     for H in (Hcc, Hpp):
         k = H.shape[1]
-        H[:, np.arange(k), np.arange(k)] += np.clip(np.einsum("nii->ni", H), dt(1e-6), dt(1e32)) / dt(radius)
+        damp.append(np.clip(np.einsum("nii->ni", H), dt(1e-6), dt(1e32)) / dt(radius))
+        H[:, np.arange(k), np.arange(k)] += damp[-1]
     E = bp["JcJp"].astype(dt) * sc[np.maximum(oc, 0)][:, :, None] * sp[op][:, None, :]
     E[~m] = 0
-    return dict(Hcc=Hcc, Hpp=Hpp, E=E, gc=gc, gp=gp, oc=oc, op=op, m=m, sc=sc, sp=sp), scale
+    return dict(Hcc=Hcc, Hpp=Hpp, E=E, gc=gc, gp=gp, oc=oc, op=op, m=m, sc=sc, sp=sp, dc=damp[0], dp=damp[1]), scale
 
 
 def block_step(p, bp, radius, scale, dt):
     """One Ceres LM step from per-block products `bp` (oracle.block_products or record_blocks) in numpy dtype `dt` (np.longdouble = x87
     extended precision on the x86 hosts used here; numpy.linalg has no longdouble, hence the hand-written 3x3 inverses and Cholesky):
     block_system, point elimination, dense solve, back-substitution.  Returns (camera step [n_free, 6], scale, S, point step [n_points, 3])."""
+    r = block_step_full(p, bp, radius, scale, dt)
+    return r["delta_c"], r["scale"], r["S"], r["delta_p"]
+
+
+def block_step_full(p, bp, radius, scale, dt):
+    """block_step with everything the step statistics of pba_step are made of.  Returns dict(delta_c, delta_p, scale, S, rhs (the reduced
+    system: scaled, damped, as pba_get_reduced_system returns it), gradient_max_norm, gradient_norm (unscaled gradient over cameras and
+    points), model_cost_change (Ceres: -m^T (r + m / 2) with m = J step), step_norm)."""
     y, scale = block_system(p, bp, radius, scale, dt)
     nf, npt = len(y["Hcc"]), p.n_points
     oc, op, m, E = y["oc"], y["op"], y["m"], y["E"]
@@ -318,7 +328,17 @@ def block_step(p, bp, radius, scale, dt):
     t = y["gp"].copy()                                         # y_p = C^-1 (g_p - E^T y_c)
     np.subtract.at(t, op[m], np.einsum("nij,ni->nj", E[m], yc[oc[m]]))
     yp = np.einsum("nij,nj->ni", Ci, t)
-    return -(yc * y["sc"]), scale, S, -(yp * y["sp"])
+    d_c, d_p = -(yc * y["sc"]), -(yp * y["sp"])
+    # model cost change = y^T g - y^T (Js^T Js) y / 2, with Js^T Js = H - damping, from the blocks (no use of H y = g)
+    Hy_c = np.einsum("nij,nj->ni", y["Hcc"], yc) - y["dc"] * yc
+    np.add.at(Hy_c, oc[m], np.einsum("nij,nj->ni", E[m], yp[op[m]]))
+    Hy_p = np.einsum("nij,nj->ni", y["Hpp"], yp) - y["dp"] * yp
+    np.add.at(Hy_p, op[m], np.einsum("nij,ni->nj", E[m], yc[oc[m]]))
+    model = (yc * y["gc"]).sum() + (yp * y["gp"]).sum() - ((yc * Hy_c).sum() + (yp * Hy_p).sum()) / 2
+    g = np.concatenate([(y["gc"] / y["sc"]).reshape(-1), (y["gp"] / y["sp"]).reshape(-1)])
+    return dict(delta_c=d_c, delta_p=d_p, scale=scale, S=S, rhs=rhs, gradient_max_norm=float(np.abs(g).max()),
+                gradient_norm=float(np.sqrt((g * g).sum())), model_cost_change=float(model),
+                step_norm=float(np.sqrt((d_c * d_c).sum() + (d_p * d_p).sum())))
 
 
 def backward_error(p, bp, radius, scale, d_c, d_p):
@@ -408,3 +428,36 @@ def step_accuracy(p, iterations):
                              data_shift=float(np.abs(d_o - d_x).max() / nrm)))
             scale_x = scale_x1
     return rows
+
+
+def restated_twin(p, n_iterations, ulp_seed=None, radius=1e4, max_radius=1e16, min_relative_decrease=1e-3):
+    """Cost per iteration of a float64 trust-region loop (Ceres' Levenberg-Marquardt: accept when rho = cost change / model cost change
+    exceeds min_relative_decrease, radius /= max(1/3, 1 - (2 rho - 1)^3)) whose step is block_step_full on the oracle's per-block
+    products: a double-precision run of the SAME algorithm that shares no linear algebra with the oracle (point-by-point elimination,
+    hand-written Cholesky against the oracle's SchurEliminator and dense solve).  The oracle's own twins (dual-number and analytic
+    Jacobians) share one solver, so their distance to the extended-precision referee shows the rounding of the Jacobians only; this
+    twin adds the rounding of the step itself, which conditioning amplifies (step_accuracy: 1e-10 .. 1e-8 of the step at cond(S) 1e4 ..
+    4e6 for any double algorithm).  ulp_seed: the block products are moved by one ulp with seeded signs (another draw from the same
+    band, as in step_accuracy).  The loop ends at the first step it would reject: only the iterations up to there are returned.
+    Returns (costs, cameras after the last accepted step)."""
+    free = [c for c in range(p.n_frames) if c != p.fixed_slot]
+    cams, xyz = p.cams.copy(), p.xyz.copy()
+    cost = oracle.cost(p, cams=cams, xyz=xyz, threads=8)[0]
+    costs, scale = [cost], None
+    rng = np.random.default_rng(ulp_seed) if ulp_seed is not None else None
+    for _ in range(n_iterations):
+        bp = oracle.block_products(p, autodiff=True, threads=8, cams=cams, xyz=xyz)
+        if rng is not None:
+            bp = {k: v * (1.0 + np.ldexp(1.0, -52) * rng.choice([-1.0, 1.0], size=v.shape)) for k, v in bp.items()}
+        s = block_step_full(p, bp, radius, scale, np.float64)
+        scale = s["scale"]
+        c1, x1 = cams.copy(), xyz + s["delta_p"]
+        c1[free] += s["delta_c"]
+        new = oracle.cost(p, cams=c1, xyz=x1, threads=8)[0]
+        rho = (cost - new) / s["model_cost_change"]
+        if not rho > min_relative_decrease:
+            break
+        cams, xyz, cost = c1, x1, new
+        radius = min(max_radius, radius / max(1.0 / 3.0, 1.0 - (2.0 * rho - 1.0) ** 3))
+        costs.append(cost)
+    return costs, cams
