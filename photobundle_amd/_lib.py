@@ -84,6 +84,12 @@ STEREO_SYMBOLS = [
     "pba_stereo_get_prefiltered", "pba_stereo_get_timing", "pba_stereo_validate_params",
 ]
 
+# every symbol include/pba_sgm.h declares (the semi-global matcher's own handle; photobundle_amd/stereo.py)
+SGM_SYMBOLS = [
+    "pba_sgm_default_params", "pba_sgm_validate_params", "pba_sgm_create", "pba_sgm_compute", "pba_sgm_last_error",
+    "pba_sgm_destroy", "pba_sgm_get_timing", "pba_sgm_get_stage",
+]
+
 
 def lib():
     """Returns the loaded CDLL; raises EngineUnavailable (never falls back) when the library is not built."""

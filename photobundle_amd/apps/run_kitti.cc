@@ -9,8 +9,9 @@
 // The config file is the reference's (config/kitti_stereo.cfg keys) plus `DataDirectory` and `DepthSource`; `Trajectory` is
 // the KITTI pose text file of frame-to-frame initial poses (reference data/kitti_init_poor/*.txt).
 //     DepthSource = files    (default) depth from depth_%06d.bin
-//     DepthSource = stereo   depth from the left/right pair on the device: the config's StereoAlgorithm (BlockMatching) +
-//                            disparityToDepth with Bf = baseline * fx (reference apps/run_kitti.cc:29, src/dataset.cc:105-137)
+//     DepthSource = stereo   depth from the left/right pair on the device: the config's StereoAlgorithm (BlockMatching, or
+//                            SGM / SemiGlobalMatching with the reference's SgmStereo keys) + disparityToDepth with
+//                            Bf = baseline * fx (reference apps/run_kitti.cc:29, src/dataset.cc:105-137)
 #include <algorithm>
 #include <array>
 #include <cctype>
@@ -25,6 +26,7 @@
 #include "../host/photobundle.h"
 #include "../host/photobundle_pyramid.h"
 #include "../host/pose_utils.h"
+#include "../host/sgm_stereo.h"
 #include "../host/stereo_algorithm.h"
 #include "../host/utils.h"
 
@@ -106,6 +108,7 @@ struct Sequence {
   int rows = 0, cols = 0, num_levels = 1;
   float Bf = 0.f;
   std::unique_ptr<StereoAlgorithm> stereo;
+  std::unique_ptr<SgmStereo> sgm;
 
   explicit Sequence(const std::string& config) : cf(new utils::ConfigFile(config)) {
     data = cf->get<std::string>("DataDirectory");
@@ -120,7 +123,12 @@ struct Sequence {
     Bf = (float)(calib.b() * calib.fx());
     num_levels = cf->get<int>("numLevels", 1);   // > 1: coarse-to-fine (photobundle_pyramid path)
   }
-  void start() { if (depth_source == "stereo") stereo.reset(new StereoAlgorithm(*cf)); }
+  // StereoAlgorithm = SGM | SemiGlobalMatching builds the semi-global matcher; every other value goes to StereoAlgorithm
+  void start() {
+    if (depth_source != "stereo") return;
+    if (SgmStereo::selectedBy(*cf)) sgm.reset(new SgmStereo(SgmStereo::Config::fromConfigFile(*cf)));
+    else stereo.reset(new StereoAlgorithm(*cf));
+  }
   // frame f_i into img / depth; false when the image is missing (the sequence ends)
   bool read(int f_i) {
     char name[64];
@@ -129,11 +137,12 @@ struct Sequence {
     if (!readPgm(data + name, img, r2, c2)) return false;
     if (r2 != rows || c2 != cols) throw std::runtime_error("frame size changed");
     depth.resize((size_t)rows * cols);
-    if (stereo) {
+    if (stereo || sgm) {
       std::snprintf(name, sizeof(name), "/right_%06d.pgm", f_i);
       if (!readPgm(data + name, right, r2, c2)) throw std::runtime_error(std::string("cannot read ") + (name + 1));
       if (r2 != rows || c2 != cols) throw std::runtime_error("right frame size differs");
-      stereo->depth(img.data(), right.data(), ImageSize(rows, cols), Bf, depth.data());
+      if (sgm) sgm->depth(img.data(), right.data(), ImageSize(rows, cols), Bf, depth.data());
+      else stereo->depth(img.data(), right.data(), ImageSize(rows, cols), Bf, depth.data());
     } else {
       std::snprintf(name, sizeof(name), "/depth_%06d.bin", f_i);
       std::ifstream dfs(data + name, std::ios::binary);
