@@ -246,7 +246,9 @@ int pba_frontend_zncc_probe(pba_engine* e, int32_t n, const double* uv, const fl
  * Limit: at most 32 FREE cameras (n_frames <= max_frames <= PBA_MAX_FRAMES).  The window shape picks the path at
  * pba_set_cameras: up to 15 free cameras the narrow kernels and drivers, 16 to 32 the wide chain (host-stepped driver).
  * A wide window refuses the multi-rank transports (pba_comm_*), the inverse-depth mode and the precision-sweep flags:
- * PBA_ERR_INVALID with a message in pba_last_error, whichever of the calls comes second. */
+ * PBA_ERR_INVALID with a message in pba_last_error, whichever of the calls comes second.
+ * pba_set_points_constant (after pba_set_problem, before or after pba_set_cameras / pba_set_inverse_depth) turns the passes
+ * below into the pose-only problem; pba_set_problem switches it off again. */
 int pba_set_problem(pba_engine* e, int32_t n_points, const double* xyz, const double* desc,
                     int32_t n_obs, const int32_t* obs_point, const int32_t* obs_slot, const double* weights);
 /* cams6: [n_frames][6]; fixed_slot: SetParameterBlockConstant (photobundle.cc:809-813), -1 for none. */
@@ -259,6 +261,19 @@ int pba_set_cameras(pba_engine* e, const double* cams6, int32_t n_frames, int32_
  * mode off again. */
 int pba_set_inverse_depth(pba_engine* e, const double* rays6, const double* rho);
 int pba_get_points_world(pba_engine* e, double* xyz);
+/* Pose-only solves.  Ceres: SetParameterBlockConstant on every point block.  on != 0: pba_linearize / pba_step / pba_accept / pba_solve
+ * treat every point as constant; cameras other than fixed_slot stay free.  Call after pba_set_problem; pba_set_problem switches it off
+ * again (as it does for inverse depth).  Semantics are Ceres' for the reduced program: its parameter blocks are the free cameras that
+ * have at least one residual block; the residual blocks of the constant camera leave the program and their loss-corrected cost is
+ * summary.fixed_cost (initial_cost and final_cost include it; the per-iteration cost, num_residual_blocks and num_residuals count the
+ * program only; pba_linearize's cost stays the sum over ALL residual blocks).  The normal equations are block diagonal, one 6x6 block
+ * per free camera solved by an exact Cholesky, at every window shape (2..32 slots); gradient norms, step_norm, x_norm and
+ * model_cost_change run over the program's camera columns.  pba_get_state / pba_get_points_world return the points byte for byte as
+ * set; pba_get_reduced_system returns the block-diagonal system in the dense n x n layout.  pba_solve runs the host-stepped driver and
+ * returns PBA_ERR_INVALID before any launch when no free camera has a residual block.  Refused with PBA_ERR_INVALID and a message,
+ * whichever call comes second: the multi-rank transports, the precision-sweep flags, pba_solve_batch with such an engine (and, on
+ * windows of 16..32 free cameras, what pba_set_cameras refuses there).  Switched off again the engine solves as a fresh one does. */
+int pba_set_points_constant(pba_engine* e, int32_t on);
 /* Current (best) state; either pointer may be NULL. */
 int pba_get_state(pba_engine* e, double* cams6, double* xyz);
 

@@ -12,6 +12,11 @@
 //     DepthSource = stereo   depth from the left/right pair on the device: the config's StereoAlgorithm (BlockMatching, or
 //                            SGM / SemiGlobalMatching with the reference's SgmStereo keys) + disparityToDepth with
 //                            Bf = baseline * fx (reference apps/run_kitti.cc:29, src/dataset.cc:105-137)
+//     InitialPose = trajectory  (default) every frame's initial pose comes from the `Trajectory` file; the sequence ends with it
+//     InitialPose = track       the driver produces its own: from frame 2 on the start pose is the constant-velocity prediction from
+//                            the two latest refined poses, refined by trackFrame (pose-only alignment against the scene points)
+//                            before addFrame receives it.  `Trajectory` is optional and supplies frames 0 and 1 only (identity and
+//                            zero motion without it); the sequence ends with the images.  Not available with -b.
 #include <algorithm>
 #include <array>
 #include <cctype>
@@ -100,7 +105,8 @@ static void dumpResult(const std::string& fn, int frame, const PhotometricBundle
 // One sequence: its config, data, initial trajectory and depth source (what main() reads for the single run, and per -b entry)
 struct Sequence {
   std::unique_ptr<utils::ConfigFile> cf;
-  std::string data, depth_source, output, results;
+  std::string data, depth_source, output, results, initial_pose;
+  bool track = false;
   Calibration calib;
   EigenAlignedContainer_<Mat44> T_init;
   std::vector<uint8_t> img, right;
@@ -111,12 +117,17 @@ struct Sequence {
   std::unique_ptr<SgmStereo> sgm;
 
   explicit Sequence(const std::string& config) : cf(new utils::ConfigFile(config)) {
+    initial_pose = cf->get<std::string>("InitialPose", "trajectory");
+    std::transform(initial_pose.begin(), initial_pose.end(), initial_pose.begin(), [](unsigned char c) { return std::tolower(c); });
+    if (initial_pose != "trajectory" && initial_pose != "track") throw std::runtime_error("InitialPose must be trajectory or track, not " + initial_pose);
+    track = initial_pose == "track";
     data = cf->get<std::string>("DataDirectory");
     calib = loadCalibration(data + "/calib.txt");
     depth_source = cf->get<std::string>("DepthSource", "files");
     std::transform(depth_source.begin(), depth_source.end(), depth_source.begin(), [](unsigned char c) { return std::tolower(c); });
     if (depth_source != "files" && depth_source != "stereo") throw std::runtime_error("DepthSource must be files or stereo, not " + depth_source);
-    T_init = loadPosesKittiFormat(cf->get<std::string>("trajectory"));
+    if (!track) T_init = loadPosesKittiFormat(cf->get<std::string>("trajectory"));
+    else if (!cf->get<std::string>("trajectory", "").empty()) T_init = loadPosesKittiFormat(cf->get<std::string>("trajectory"));
     char name[64];
     std::snprintf(name, sizeof(name), "/image_%06d.pgm", 0);
     if (!readPgm(data + name, img, rows, cols)) throw std::runtime_error("cannot read the first frame");
@@ -233,6 +244,7 @@ int main(int argc, char** argv) {
         seqs.emplace_back(new Sequence(f[0]));
         seqs.back()->output = f[1];
         seqs.back()->results = f[2];
+        if (seqs.back()->track) { std::fprintf(stderr, "error: -b does not take InitialPose = track (%s): the batched driver has no tracker\n", f[0].c_str()); return 1; }
       }
       return runBatch(seqs, full_precision);
     } catch (const std::exception& ex) {
@@ -249,12 +261,31 @@ int main(int argc, char** argv) {
     std::unique_ptr<PhotometricBundleAdjustmentPyr> photoba_pyr;
     if (q.num_levels > 1) photoba_pyr.reset(new PhotometricBundleAdjustmentPyr(q.num_levels, q.calib, ImageSize(rows, cols), {*q.cf}));
     else photoba.reset(new PhotometricBundleAdjustment(q.calib, ImageSize(rows, cols), {*q.cf}));
-    for (int f_i = 0; f_i < (int)q.T_init.size() && !gStop; ++f_i) {
+    Mat44 T_last = Mat44::Identity();      // (InitialPose = track) the frame-to-frame pose the previous frame was added with
+    for (int f_i = 0; (q.track || f_i < (int)q.T_init.size()) && !gStop; ++f_i) {
       if (!q.read(f_i)) break;
       std::printf("Frame %05d\n", f_i);
+      Mat44 T = f_i < (int)q.T_init.size() ? q.T_init[f_i] : Mat44::Identity();
+      if (q.track && f_i >= 2) {
+        // constant velocity: the latest refined frame-to-frame motion repeats (T_i = inv(T_w_i) * T_w_(i-1), trajectory.h); before the
+        // first optimisation no pose has been refined and the motion the previous frame was added with stands in
+        const size_t m = result.poses.size();
+        const Mat44 T_pred = m >= 2 ? Mat44(result.poses[m - 1].inverse() * result.poses[m - 2]) : T_last;
+        TrackResult tr;
+        T = photoba_pyr ? photoba_pyr->trackFrame(q.img.data(), T_pred, TrackOptions(), &tr) : photoba->trackFrame(q.img.data(), T_pred, TrackOptions(), &tr);
+        if (!tr.tracked) {
+          std::fprintf(stderr, "frame %d was not tracked (%s): keeping the constant-velocity prediction\n", f_i, tr.message.c_str());
+          T = T_pred;
+        }
+        std::printf("track frame %d tracked %d points %d iterations %d cost %.6e -> %.6e pose", f_i, (int)tr.tracked, tr.numPoints, tr.numIterations,
+                    tr.initialCost, tr.finalCost);
+        for (int a = 0; a < 3; ++a) for (int b = 0; b < 4; ++b) std::printf(" %.17g", T(a, b));
+        std::printf("\n");
+      }
+      T_last = T;
       result.initialCost = -1.0;    // the class only touches `result` when an optimisation ran (photobundle.cc:857)
-      if (photoba_pyr) photoba_pyr->addFrame(q.img.data(), q.depth.data(), q.T_init[f_i], &result);
-      else photoba->addFrame(q.img.data(), q.depth.data(), q.T_init[f_i], &result);
+      if (photoba_pyr) photoba_pyr->addFrame(q.img.data(), q.depth.data(), T, &result);
+      else photoba->addFrame(q.img.data(), q.depth.data(), T, &result);
       if (!results.empty() && result.initialCost >= 0.0) dumpResult(results, f_i, result);
     }
     writePoses(output, result, full_precision);

@@ -11,6 +11,7 @@
 #include "pba_resident.h"
 #include "pba_wide.h"
 #include "pba_batch.h"
+#include "pba_pose.h"
 
 #include <algorithm>
 #include <chrono>
@@ -154,6 +155,14 @@ struct pba_engine {
   int32_t* d_wpair_chunk = nullptr; // [n_pairs + 1]
   double* d_wsums = nullptr;        // [wide_chunks][kWideVals]
   int wide_chunks = 0, wide_pt_blocks = 0;
+
+  // pose-only solves (pba_set_points_constant, pba_pose.h): everything on first use
+  bool points_const = false;
+  bool pose_xyz_synced = false;     // both point parities hold the same (constant) points
+  int pose_sums_cur = -1;           // parity whose linearisation d_pose_sums was reduced from, -1 none
+  int pose_grid = 0;                // workgroups of the last k_pose_system launch (rows of d_pose_partial)
+  double* d_pose_partial = nullptr; // [kPoseMaxGrid][n_frames * kPoseVals]
+  double* d_pose_sums = nullptr;    // [n_frames * kPoseVals + 2]
 
   // batched solves (pba_solve_batch, pba_batch.h): the window table lives with the batch's FIRST engine (grow-only), whose stream
   // carries the batch; while a batch runs every engine's `stream` names that stream and `stream_own` keeps its own
@@ -785,6 +794,7 @@ void pba_destroy(pba_engine* e) {
   dev_free(&e->d_lm);
   dev_free(&e->d_log);
   dev_free(&e->d_res_sync);
+  dev_free(&e->d_pose_partial); dev_free(&e->d_pose_sums);
   dev_free(&e->d_wfac); dev_free(&e->d_wpt_part); dev_free(&e->d_went); dev_free(&e->d_wchunk); dev_free(&e->d_wpair_chunk); dev_free(&e->d_wsums);
   for (int k = 0; k < 2 * pba_engine::kEvPairs; ++k) if (e->ev[k]) (void)hipEventDestroy(e->ev[k]);
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -1252,6 +1262,8 @@ int pba_set_problem(pba_engine* e, int32_t n_points, const double* xyz, const do
   e->wide_ready = false;
   e->have_problem = true;
   e->inverse_depth = false;         // back to the reference's free world points until pba_set_inverse_depth says otherwise
+  e->points_const = false;          // ... and to free points until pba_set_points_constant says otherwise
+  e->pose_xyz_synced = false; e->pose_sums_cur = -1;
   e->have_lin = false;
   e->lin_valid[0] = e->lin_valid[1] = false;
   return PBA_OK;
@@ -1314,6 +1326,7 @@ int pba_set_cameras(pba_engine* e, const double* cams6, int32_t n_frames, int32_
   e->have_cams = true;
   e->have_lin = false;
   e->lin_valid[0] = e->lin_valid[1] = false;
+  e->pose_sums_cur = -1;
   return PBA_OK;
 }
 
@@ -1363,6 +1376,38 @@ int pba_set_inverse_depth(pba_engine* e, const double* rays6, const double* rho)
   e->inverse_depth = true;
   e->have_lin = false;
   e->lin_valid[0] = e->lin_valid[1] = false;
+  e->pose_xyz_synced = false; e->pose_sums_cur = -1;
+  return PBA_OK;
+}
+
+// Why the pose-only mode cannot run with what the engine has been given (nullptr: it can)
+static const char* pose_refusal(const pba_engine* e) {
+  if (e->comm.multi()) return "multi-rank solves (pba_comm_*) are not built for the points-constant mode";
+  if ((e->cfg.flags >> 1) & 3) return "the precision-sweep sampler modes (pba_config.flags bits 1-2) are not built for the points-constant mode";
+  return nullptr;
+}
+
+int pba_set_points_constant(pba_engine* e, int32_t on) {
+  if (!e) return PBA_ERR_INVALID;
+  if (!e->have_problem) return fail(e, PBA_ERR_STATE, "call order violated: pba_set_points_constant before pba_set_problem");
+  PBA_NOT_POISONED(e);
+  if (on) {
+    const char* why = pose_refusal(e);
+    if (why) return fail(e, PBA_ERR_INVALID, "pba_set_points_constant: %s", why);
+  }
+  e->points_const = on != 0;
+  e->pose_xyz_synced = false; e->pose_sums_cur = -1;
+  e->have_lin = false;
+  e->lin_valid[0] = e->lin_valid[1] = false;
+  return PBA_OK;
+}
+
+// The constant points live in BOTH parities (the candidate pass reads the candidate parity, pba_accept flips it): a device-to-device
+// copy of the current one, byte for byte, once per problem.
+static int pose_sync_points(pba_engine* e) {
+  if (e->pose_xyz_synced) return PBA_OK;
+  HIP_TRY(e, hipMemcpyAsync(e->d_xyz[1 - e->cur], e->d_xyz[e->cur], sizeof(double) * 3 * e->n_points, hipMemcpyDeviceToDevice, e->stream));
+  e->pose_xyz_synced = true;
   return PBA_OK;
 }
 
@@ -1387,7 +1432,9 @@ int pba_linearize(pba_engine* e, double* cost) {
   { const int rc0 = check_ready(e, "pba_linearize"); if (rc0) return rc0; }
   PBA_NOT_POISONED(e);
   HIP_TRY(e, hipSetDevice(e->cfg.device));
+  if (e->points_const) { const int rcp = pose_sync_points(e); if (rcp) return rcp; }
   if (!e->lin_valid[e->cur]) {
+    if (e->pose_sums_cur == e->cur) e->pose_sums_cur = -1;
     SampleParams sp = make_sample_params(e, e->cur);
     ev_begin(e, 0);
     launch_sample<true>(e, sp);
@@ -1413,6 +1460,110 @@ int pba_linearize(pba_engine* e, double* cost) {
   return PBA_OK;
 }
 
+// Waits for the device to publish the scalar block of step `seq` and unpacks it (the end of every pba_step).
+static int wait_step_scalars(pba_engine* e, unsigned long long seq, bool multi, pba_step_info* out) {
+  // wait for the device to publish this step's scalar block (host-mapped memory, no driver round trip)
+  {
+    volatile unsigned long long* h_seq = reinterpret_cast<volatile unsigned long long*>(e->h_scal + kNumScal);
+    unsigned long spins = 0;
+    double t_first = -1.0;
+    { const int rcc = comm_failed(e); if (rcc) return rcc; }
+    while (*h_seq != seq) {
+      { const int rcc = comm_failed(e); if (rcc) return rcc; }
+      // hipStreamQuery is not free for the device (it showed up as a ~6 us bubble in front of the next kernel), so it only
+      // serves as a watchdog here: roughly every 50 ms of spinning
+      if ((++spins & 0x3ffffff) == 0) {
+        const hipError_t q = hipStreamQuery(e->stream);
+        if (q != hipSuccess && q != hipErrorNotReady) return fail(e, PBA_ERR_HIP, "stream error while waiting: %s", hipGetErrorString(q));
+        if (q == hipSuccess && *h_seq != seq) return fail(e, PBA_ERR_HIP, "step finished without publishing its scalars");
+        const double t = wall_seconds();
+        if (t_first < 0.0) t_first = t;
+        else if (t - t_first > e->wait_timeout_s) {
+          e->poisoned = true;
+          return fail(e, multi ? PBA_ERR_COMM : PBA_ERR_HIP, "timed out after %.0f s waiting for step %llu", e->wait_timeout_s, seq);
+        }
+      }
+    }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    // the sequence number may already have been there when the wait was entered: the error word is checked on the way out too
+    { const int rcc = comm_failed(e); if (rcc) return rcc; }
+  }
+  if (e->profile) { HIP_TRY(e, hipStreamSynchronize(e->stream)); ev_collect(e); }
+  double s[kNumScal];
+  for (int k = 0; k < kNumScal; ++k) s[k] = reinterpret_cast<volatile double*>(e->h_scal)[k];
+  out->cost = s[kCostLin];
+  out->gradient_max_norm = std::max(s[kGmaxPts], s[kGmaxCams]);
+  out->gradient_norm = std::sqrt(s[kGnorm2Pts] + s[kGnorm2Cams]);
+  out->model_cost_change = s[kMccPts] + s[kMccCams];
+  out->step_norm = std::sqrt(s[kStep2Pts] + s[kStep2Cams]);
+  out->x_norm = std::sqrt(s[kX2Pts] + s[kX2Cams]);
+  out->candidate_cost = s[kCandCost];
+  out->linear_solver_ok = (s[kSolveOk] > 0.5 && s[kSchurFail] < 0.5) ? 1 : 0;
+  out->eval_ok = (s[kEvalFailCand] < 0.5 && std::isfinite(s[kCandCost])) ? 1 : 0;
+  if (s[kEvalFailLin] > 0.5) return fail(e, PBA_ERR_NUMERIC, "non-finite residual block at the linearisation point");
+  return PBA_OK;
+}
+
+// pba_step of the pose-only mode (pba_pose.h): per-camera sums of the stored linearisation (once per linearisation), the block-diagonal
+// damped solve, the candidate pass at the candidate cameras with the unchanged points, the candidate cost.
+static int pose_step(pba_engine* e, double radius, int32_t init_scale, const pba_solver_options* o, pba_step_info* out, int grad_only) {
+  const int cur = e->cur, cand = 1 - e->cur;
+  int rc;
+  if ((rc = pose_sync_points(e))) return rc;
+  if ((rc = dev_alloc(e, &e->d_pose_partial, (size_t)kPoseMaxGrid * kMaxFramesWide * kPoseVals))) return rc;
+  if ((rc = dev_alloc(e, &e->d_pose_sums, (size_t)kMaxFramesWide * kPoseVals + 2))) return rc;
+  const bool reduce = e->pose_sums_cur != cur;
+  if (reduce) {
+    PoseSystemParams ps{};
+    ps.xyz = e->d_xyz[cur]; ps.rays = e->inverse_depth ? e->d_rays : nullptr; ps.geom = e->d_geom[cur]; ps.rec = e->d_rec[cur];
+    ps.obs_point = e->d_obs_point; ps.obs_slot = e->d_obs_slot; ps.partial = e->d_pose_partial; ps.rec_stride = e->rec_stride;
+    ps.n_obs = e->n_obs; ps.n_frames = e->n_frames; ps.fx = e->cfg.fx; ps.fy = e->cfg.fy;
+    e->pose_grid = std::max(1, std::min(kPoseMaxGrid, (e->n_obs + kPoseThreads - 1) / kPoseThreads));
+    ev_begin(e, 2);
+    hipLaunchKernelGGL(k_pose_system, dim3(e->pose_grid), dim3(kPoseThreads), 0, e->stream, ps);
+    ev_end(e, 2);
+    HIP_TRY(e, hipGetLastError());
+  }
+  PoseSolveParams so{};
+  so.partial = e->d_pose_partial; so.sums = e->d_pose_sums; so.block_cost = e->d_block_cost[cur]; so.block_fail = e->d_block_fail[cur];
+  so.cams = e->d_cams[cur]; so.cams_cand = e->d_cams[cand]; so.delta_c = e->d_delta_c; so.sc = e->d_sc;
+  so.S_dbg = (e->cfg.flags & 1) ? e->d_S : nullptr; so.rhs_dbg = e->d_rhs; so.scal = e->d_scal;
+  so.geom = e->d_geom[cur]; so.geom_cand = e->d_geom[cand];
+  so.n_parts = e->pose_grid; so.n_cost_blocks = e->cost_blocks[cur]; so.reduce = reduce ? 1 : 0;
+  so.n_frames = e->n_frames; so.n_free = e->n_free; so.fixed_slot = e->fixed_slot; so.init_scale = init_scale; so.jacobi = o->jacobi_scaling;
+  so.grad_only = grad_only; so.radius = radius; so.min_diag = o->min_lm_diagonal; so.max_diag = o->max_lm_diagonal;
+  ev_begin(e, 3);
+  hipLaunchKernelGGL(k_pose_solve, dim3(1), dim3(kPoseThreads), 0, e->stream, so);
+  ev_end(e, 3);
+  HIP_TRY(e, hipGetLastError());
+  e->pose_sums_cur = cur;
+  const unsigned long long seq = ++e->seq;
+  unsigned long long* h_seq_dev = reinterpret_cast<unsigned long long*>(e->h_scal_dev + kNumScal);
+  if (!grad_only) {
+    // candidate point: Jacobian pass when speculating on acceptance, else cost pass; the points are the current ones
+    SampleParams sp = make_sample_params(e, cand);
+    if (e->speculate) {
+      ev_begin(e, 0);
+      launch_sample<true>(e, sp);
+      ev_end(e, 0);
+      e->jac_passes++;
+    } else {
+      ev_begin(e, 1);
+      launch_sample<false>(e, sp);
+      ev_end(e, 1);
+      e->cost_passes++;
+    }
+    e->cost_blocks[cand] = e->sample_grid;
+    e->lin_valid[cand] = e->speculate;
+    hipLaunchKernelGGL(k_pose_finalize, dim3(1), dim3(kPoseThreads), 0, e->stream, (const double*)e->d_block_cost[cand],
+                       (const int32_t*)e->d_block_fail[cand], e->sample_grid, e->d_scal, e->h_scal_dev, h_seq_dev, seq);
+  } else {
+    hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, e->stream, e->d_scal, e->h_scal_dev, h_seq_dev, seq, (const double*)nullptr, 1);
+  }
+  HIP_TRY(e, hipGetLastError());
+  return wait_step_scalars(e, seq, false, out);
+}
+
 int pba_step(pba_engine* e, double radius, int32_t init_scale, const pba_solver_options* o, pba_step_info* out) {
   return pba_internal_step(e, radius, init_scale, o, out, 0);
 }
@@ -1425,6 +1576,7 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
   if (!e->have_lin) return fail(e, PBA_ERR_STATE, "call order violated: pba_step before pba_linearize");
   PBA_NOT_POISONED(e);
   HIP_TRY(e, hipSetDevice(e->cfg.device));
+  if (e->points_const) return pose_step(e, radius, init_scale, o, out, grad_only);
   const int cur = e->cur, cand = 1 - e->cur;
   const int n = 6 * e->n_free;
   const bool multi = e->comm.multi();
@@ -1598,46 +1750,7 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
                        (const double*)(multi ? e->d_xchg : nullptr), e->comm.world);
     HIP_TRY(e, hipGetLastError());
   }
-  // wait for the device to publish this step's scalar block (host-mapped memory, no driver round trip)
-  {
-    volatile unsigned long long* h_seq = reinterpret_cast<volatile unsigned long long*>(e->h_scal + kNumScal);
-    unsigned long spins = 0;
-    double t_first = -1.0;
-    { const int rcc = comm_failed(e); if (rcc) return rcc; }
-    while (*h_seq != seq) {
-      { const int rcc = comm_failed(e); if (rcc) return rcc; }
-      // hipStreamQuery is not free for the device (it showed up as a ~6 us bubble in front of the next kernel), so it only
-      // serves as a watchdog here: roughly every 50 ms of spinning
-      if ((++spins & 0x3ffffff) == 0) {
-        const hipError_t q = hipStreamQuery(e->stream);
-        if (q != hipSuccess && q != hipErrorNotReady) return fail(e, PBA_ERR_HIP, "stream error while waiting: %s", hipGetErrorString(q));
-        if (q == hipSuccess && *h_seq != seq) return fail(e, PBA_ERR_HIP, "step finished without publishing its scalars");
-        const double t = wall_seconds();
-        if (t_first < 0.0) t_first = t;
-        else if (t - t_first > e->wait_timeout_s) {
-          e->poisoned = true;
-          return fail(e, multi ? PBA_ERR_COMM : PBA_ERR_HIP, "timed out after %.0f s waiting for step %llu", e->wait_timeout_s, seq);
-        }
-      }
-    }
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    // the sequence number may already have been there when the wait was entered: the error word is checked on the way out too
-    { const int rcc = comm_failed(e); if (rcc) return rcc; }
-  }
-  if (e->profile) { HIP_TRY(e, hipStreamSynchronize(e->stream)); ev_collect(e); }
-  double s[kNumScal];
-  for (int k = 0; k < kNumScal; ++k) s[k] = reinterpret_cast<volatile double*>(e->h_scal)[k];
-  out->cost = s[kCostLin];
-  out->gradient_max_norm = std::max(s[kGmaxPts], s[kGmaxCams]);
-  out->gradient_norm = std::sqrt(s[kGnorm2Pts] + s[kGnorm2Cams]);
-  out->model_cost_change = s[kMccPts] + s[kMccCams];
-  out->step_norm = std::sqrt(s[kStep2Pts] + s[kStep2Cams]);
-  out->x_norm = std::sqrt(s[kX2Pts] + s[kX2Cams]);
-  out->candidate_cost = s[kCandCost];
-  out->linear_solver_ok = (s[kSolveOk] > 0.5 && s[kSchurFail] < 0.5) ? 1 : 0;
-  out->eval_ok = (s[kEvalFailCand] < 0.5 && std::isfinite(s[kCandCost])) ? 1 : 0;
-  if (s[kEvalFailLin] > 0.5) return fail(e, PBA_ERR_NUMERIC, "non-finite residual block at the linearisation point");
-  return PBA_OK;
+  return wait_step_scalars(e, seq, multi, out);
 }
 
 int pba_accept(pba_engine* e) {
@@ -1646,6 +1759,7 @@ int pba_accept(pba_engine* e) {
   e->lin_valid[e->cur] = false;
   e->cur = 1 - e->cur;
   e->have_lin = e->lin_valid[e->cur];
+  e->pose_sums_cur = -1;
   return PBA_OK;
 }
 
@@ -1681,6 +1795,8 @@ int pba_comm_init_rccl(pba_engine* e, const void* id128, int32_t rank, int32_t w
   if (!e || !id128 || world < 1 || rank < 0 || rank >= world) return PBA_ERR_INVALID;
   if (world > 1 && e->have_cams && e->wide)
     return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for wide windows (%d free cameras)", e->n_free);
+  if (world > 1 && e->points_const)
+    return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for the points-constant mode (pba_set_points_constant)");
   PBA_NOT_POISONED(e);
   HIP_TRY(e, hipSetDevice(e->cfg.device));
   if (e->comm.init_rccl(id128, rank, world)) return fail(e, PBA_ERR_COMM, "%s", e->comm.err.c_str());
@@ -1691,6 +1807,8 @@ int pba_comm_init_callback(pba_engine* e, pba_allreduce_fn fn, void* ctx, int32_
   if (!e || !fn || world < 1 || rank < 0 || rank >= world) return PBA_ERR_INVALID;
   if (world > 1 && e->have_cams && e->wide)
     return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for wide windows (%d free cameras)", e->n_free);
+  if (world > 1 && e->points_const)
+    return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for the points-constant mode (pba_set_points_constant)");
   PBA_NOT_POISONED(e);
   HIP_TRY(e, hipSetDevice(e->cfg.device));
   if (e->comm.init_callback(fn, ctx, rank, world)) return fail(e, PBA_ERR_COMM, "%s", e->comm.err.c_str());
@@ -1825,8 +1943,22 @@ int64_t pba_internal_local_blocks(const pba_engine* e) { return e->n_obs; }
 int pba_internal_patch_len(const pba_engine* e) { return e->channels * (2 * e->cfg.radius + 1) * (2 * e->cfg.radius + 1); }
 // ---- asynchronous driver ----------------------------------------------------------------------------------------
 int pba_internal_async_capable(const pba_engine* e, const pba_solver_options* o) {
+  if (e->points_const) return 0;     // the pose-only mode is built on the host-stepped driver
   return e->use_async && fused_capable(e) && (e->comm.kind != 2 || e->comm.peer) && o->max_num_iterations < pba_engine::kMaxLog - 2 && !e->profile;
 }
+int pba_internal_points_constant(const pba_engine* e) { return e->points_const ? 1 : 0; }
+// residual blocks of the reduced program: those of the free cameras
+int64_t pba_internal_program_blocks(const pba_engine* e) {
+  if (!e->points_const || e->fixed_slot < 0) return e->n_obs;
+  int64_t n = 0;
+  for (uint8_t s : e->h_obs_slot) n += (int)s != e->fixed_slot;
+  return n;
+}
+// cost of the residual blocks of the constant camera, as the last pba_step found it (0 outside the mode)
+double pba_internal_fixed_cost(const pba_engine* e) {
+  return e->points_const ? reinterpret_cast<const volatile double*>(e->h_scal)[kPoseFixedCost] : 0.0;
+}
+int pba_internal_refuse(pba_engine* e, int code, const char* msg) { return fail(e, code, "%s", msg); }
 
 int pba_internal_ready(pba_engine* e) { return check_ready(e, "pba_solve"); }
 
@@ -2292,6 +2424,7 @@ int pba_internal_batch_validate(pba_engine* const* es, int32_t n, const pba_solv
     if (e->comm.kind != 0 || e->comm.multi()) return batch_refuse(es, i, PBA_ERR_INVALID, "multi-rank engines (pba_comm_*) solve alone");
     if (e->wide || e->n_free > kMaxFrames - 1) return batch_refuse(es, i, PBA_ERR_INVALID, "wide window (%d free cameras, a batch takes <= %d)", e->n_free, kMaxFrames - 1);
     if ((e->cfg.flags >> 1) & 3) return batch_refuse(es, i, PBA_ERR_INVALID, "the precision-sweep flags solve alone");
+    if (e->points_const) return batch_refuse(es, i, PBA_ERR_INVALID, "the points-constant mode (pba_set_points_constant) solves alone");
     if (e->profile || e->stamps) return batch_refuse(es, i, PBA_ERR_INVALID, "profiling is on (pba_set_profiling / pba_reset_counters)");
     if (!pba_internal_async_capable(e, &o[i]) || e->solve_kind != 0)
       return batch_refuse(es, i, PBA_ERR_INVALID, "the options or the environment need the host-stepped driver (max_num_iterations %d)", o[i].max_num_iterations);

@@ -12,6 +12,12 @@ int pba_internal_rank(const pba_engine* e);
 int pba_internal_is_multi(const pba_engine* e);   /* collectives are enqueued with every step */
 int64_t pba_internal_local_blocks(const pba_engine* e);
 int pba_internal_patch_len(const pba_engine* e);
+// pose-only mode (pba_set_points_constant): on / residual blocks of the reduced program (all of them outside the mode) / cost of the
+// constant camera's residual blocks as the last step found it (0 outside the mode) / sets pba_last_error and returns `code`
+int pba_internal_points_constant(const pba_engine* e);
+int64_t pba_internal_program_blocks(const pba_engine* e);
+double pba_internal_fixed_cost(const pba_engine* e);
+int pba_internal_refuse(pba_engine* e, int code, const char* msg);
 int pba_internal_allreduce_host(pba_engine* e, double* v, int n, int op);
 // candidate pass = Jacobian pass (speculative linearisation) on/off
 void pba_internal_set_speculate(pba_engine* e, int on);

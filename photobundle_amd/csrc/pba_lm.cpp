@@ -173,7 +173,13 @@ extern "C" int pba_solve(pba_engine* e, const pba_solver_options* o, pba_solver_
   std::memset(sum, 0, sizeof(*sum));
   sum->termination_type = 1;
   std::snprintf(sum->message, sizeof(sum->message), "Maximum number of iterations reached.");
-  double blocks = (double)pba_internal_local_blocks(e);
+  const bool pose = pba_internal_points_constant(e) != 0;
+  double blocks = (double)(pose ? pba_internal_program_blocks(e) : pba_internal_local_blocks(e));
+  if (pose && blocks == 0.0) {
+    // Ceres' reduced program is empty: every residual block hangs on constant parameter blocks only
+    std::snprintf(sum->message, sizeof(sum->message), "No free camera has a residual block: with every point constant the program is empty.");
+    return pba_internal_refuse(e, PBA_ERR_INVALID, sum->message);
+  }
   if (pba_internal_allreduce_host(e, &blocks, 1, 0)) return PBA_ERR_COMM;
   // ceres::Solver::Summary counts in `int` (the reference's numResiduals too): a window beyond that range is refused up front
   // instead of reporting a wrapped count (3.2 M blocks x 121 pixels x 8 channels would)
@@ -183,7 +189,7 @@ extern "C" int pba_solve(pba_engine* e, const pba_solver_options* o, pba_solver_
   }
   sum->num_residual_blocks = (int32_t)blocks;
   sum->num_residuals = (int32_t)(blocks * pba_internal_patch_len(e));
-  sum->fixed_cost = 0.0;   // every residual block has a free point
+  sum->fixed_cost = 0.0;   // every residual block has a free point unless the points are constant (below)
   const bool verbose = o->verbose && pba_internal_rank(e) == 0;
   if (pba_internal_async_capable(e, o)) {
     pba_internal_reset_pass_counts(e);
@@ -223,7 +229,9 @@ extern "C" int pba_solve(pba_engine* e, const pba_solver_options* o, pba_solver_
   if (rc) return rc;
   bool info_valid = !last;
   double x_cost = info.cost;
-  sum->initial_cost = x_cost;
+  // pose-only mode: the constant camera's residual blocks left the program; Ceres' summary adds their cost back
+  sum->fixed_cost = pba_internal_fixed_cost(e);
+  sum->initial_cost = x_cost + sum->fixed_cost;
   double minimum_cost = x_cost;
 
   pba_iteration_summary it;
@@ -350,7 +358,7 @@ extern "C" int pba_solve(pba_engine* e, const pba_solver_options* o, pba_solver_
     }
   }
   pba_internal_pass_counts(e, &sum->num_jacobian_passes, &sum->num_cost_passes);
-  sum->final_cost = minimum_cost;
+  sum->final_cost = minimum_cost + sum->fixed_cost;
   sum->num_iterations = n_it < max_out ? n_it : max_out;
   sum->total_time_in_seconds = now() - t_start;
   return PBA_OK;

@@ -202,6 +202,11 @@ class Engine:
         assert rays.shape == (self.n_points, 6) and rho.shape == (self.n_points,)
         self._check(self._L.pba_set_inverse_depth(self._h, _ptr(rays), _ptr(rho)), "pba_set_inverse_depth")
 
+    def set_points_constant(self, on=True):
+        """Pose-only mode (include/pba.h): every point is held constant, the free cameras are aligned to them.  Call after
+        set_problem / load; set_problem switches it off again."""
+        self._check(self._L.pba_set_points_constant(self._h, 1 if on else 0), "pba_set_points_constant")
+
     def get_points_world(self):
         xyz = np.zeros((self.n_points, 3))
         self._check(self._L.pba_get_points_world(self._h, _ptr(xyz)), "pba_get_points_world")

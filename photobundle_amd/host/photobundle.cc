@@ -276,7 +276,78 @@ PhotometricBundleAdjustment::PhotometricBundleAdjustment(const Calibration& cali
   check(nullptr, pba_create(&cfg, &_engine), "pba_create");
 }
 
-PhotometricBundleAdjustment::~PhotometricBundleAdjustment() { pba_destroy(_engine); }
+PhotometricBundleAdjustment::~PhotometricBundleAdjustment() { pba_destroy(_track_engine); pba_destroy(_engine); }
+
+Mat44 PhotometricBundleAdjustment::trackFrame(const uint8_t* image, const Mat44& T_init, const TrackOptions& topt, TrackResult* result) {
+  TrackResult local;
+  TrackResult& tr = result ? *result : local;
+  tr = TrackResult();
+  if (_trajectory.size() == 0) { tr.message = "no frame has been added yet"; return T_init; }
+  const Options& op = *_options_ptr;
+  const int rows = _image_size.rows, cols = _image_size.cols;
+  // the world pose addFrame would give this frame (trajectory.h: T_w_i = T_w_(i-1) * inv(T_i)) and its inverse, the camera block
+  const Mat44 T_prev = _trajectory.back();
+  const Mat44 T_c = (T_prev * T_init.inverse()).inverse();
+  const int B = std::max(op.maskBlockRadius, std::max(2, op.patchRadius));      // addFrame's visibility border
+  const int max_rows = rows - B - 1, max_cols = cols - B - 1;
+  std::vector<double> xyz, desc;
+  std::vector<int32_t> obs_point, obs_slot;
+  for (const auto& pt : _scene_points) {
+    const Vec3 Xc = TransformPoint(T_c, pt->X);
+    if (!(Xc[2] > 0.0)) continue;
+    const Vec2 uv = _calib.project(Xc);
+    const int r = (int)std::round(uv[1]), c = (int)std::round(uv[0]);
+    if (!(r >= B && r < max_rows && c >= B && c <= max_cols)) continue;
+    obs_point.push_back((int32_t)obs_point.size());
+    obs_slot.push_back(1);
+    for (int k = 0; k < 3; ++k) xyz.push_back(pt->X[k]);
+    desc.insert(desc.end(), pt->descriptor.begin(), pt->descriptor.end());
+  }
+  tr.numPoints = (int)obs_point.size();
+  if (tr.numPoints < std::max(1, topt.minPoints)) {
+    tr.message = "too few scene points inside the image: " + std::to_string(tr.numPoints) + " < " + std::to_string(topt.minPoints);
+    return T_init;
+  }
+  const Options::DescriptorType dtype = op.descriptorType;
+  if (!_track_engine) {
+    pba_config cfg;
+    std::memset(&cfg, 0, sizeof(cfg));
+    cfg.rows = rows; cfg.cols = cols; cfg.max_frames = 2; cfg.radius = op.patchRadius;
+    cfg.fx = _calib.fx(); cfg.fy = _calib.fy(); cfg.cx = _calib.cx(); cfg.cy = _calib.cy();
+    cfg.huber = op.robustThreshold; cfg.device = op.device; cfg.flags = 0;
+    cfg.channels = dtype == DescriptorType::BitPlanes ? 8 : (dtype == DescriptorType::IntensityAndGradient ? 3 : 1);
+    check(nullptr, pba_create(&cfg, &_track_engine), "pba_create (trackFrame)");
+  }
+  pba_engine* e = _track_engine;
+  // slot 0: the constant world frame (no residual block, no image); slot 1: the tracked frame
+  if (dtype != DescriptorType::Intensity) {
+    const int32_t kind = dtype == DescriptorType::BitPlanes ? PBA_DESCRIPTOR_BITPLANES : PBA_DESCRIPTOR_INTENSITY_AND_GRADIENT;
+    check(e, pba_set_frame_descriptor_u8(e, 1, image, kind, 1.0f, 1.5f), "pba_set_frame_descriptor_u8");
+  } else {
+    check(e, pba_set_frame_u8(e, 1, image), "pba_set_frame_u8");
+  }
+  const std::vector<double> patch_weights = MakePatchWeights(op.patchRadius, op.doGaussianWeighting);
+  check(e, pba_set_problem(e, tr.numPoints, xyz.data(), desc.data(), tr.numPoints, obs_point.data(), obs_slot.data(), patch_weights.data()),
+        "pba_set_problem");
+  double cams[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  PoseToParams(T_c, cams + 6);
+  check(e, pba_set_cameras(e, cams, 2, 0), "pba_set_cameras");
+  check(e, pba_set_points_constant(e, 1), "pba_set_points_constant");
+  pba_solver_options so;
+  pba_default_solver_options(&so);
+  so.max_num_iterations = topt.maxIterations;
+  so.verbose = 0;
+  pba_solver_summary summary;
+  check(e, pba_solve(e, &so, &summary, nullptr, 0), "pba_solve (trackFrame)");
+  check(e, pba_get_state(e, cams, nullptr), "pba_get_state");
+  tr.initialCost = summary.initial_cost; tr.finalCost = summary.final_cost;
+  tr.numIterations = summary.num_successful_steps + summary.num_unsuccessful_steps - 1;
+  tr.message = summary.message;
+  tr.tracked = summary.termination_type != 2;      // (2: FAILURE)
+  if (!tr.tracked) return T_init;
+  // back to addFrame's convention: T_i = inv(T_w_i) * T_w_(i-1) with inv(T_w_i) = the refined camera block
+  return ParamsToPose(cams + 6) * T_prev;
+}
 
 namespace {
 double wall_ms() {

@@ -52,6 +52,19 @@ struct IterationSummary {
 struct pba_engine;
 class PhotometricBundleAdjustmentPyr;
 
+// ---- trackFrame (new; not in the reference): align one frame to the scene points, which stay put ----
+struct TrackOptions {
+  int maxIterations = 50;
+  int minPoints = 64;                 // below it the frame is not tracked
+};
+struct TrackResult {
+  bool tracked = false;
+  int numPoints = 0;                  // scene points inside the border under T_init (one residual block each)
+  double initialCost = -1.0, finalCost = -1.0;
+  int numIterations = 0;
+  std::string message;
+};
+
 // Same public surface as the reference class (nested Options / Result, addFrame, protected optimize); the private
 // part is this implementation's own.
 class PhotometricBundleAdjustment {
@@ -69,6 +82,14 @@ class PhotometricBundleAdjustment {
   // maxValidDepth] = invalid); T: frame-to-frame pose initialisation.  `result` (optional) is overwritten whenever
   // an optimisation ran, i.e. once the sliding window is full.
   void addFrame(const uint8_t* image, const float* depth_map, const Mat44& T, Result* result = nullptr);
+
+  // Pose-only alignment (new): refines the frame-to-frame pose `T_init` of `image` -- the argument addFrame would take for this
+  // frame, and the return value is in the same convention -- against the scene points the instance holds now, every point
+  // constant (pba_set_points_constant).  Every scene point whose projection under T_init lies inside the border of addFrame's
+  // visibility test carries its stored descriptor as one residual block.  Touches neither the window, the trajectory, the mask,
+  // the scene points nor the bundle-adjustment engine: it runs on a two-slot engine of its own, created at the first call.  With
+  // fewer than minPoints points it returns T_init and tracked = false.
+  Mat44 trackFrame(const uint8_t* image, const Mat44& T_init, const TrackOptions& options = TrackOptions(), TrackResult* result = nullptr);
 
   // Several independent sequences in lockstep (new): addFrame's front-end for every instance, then ONE pba_solve_batch per kernel key
   // (patch radius, descriptor channels, Gaussian weighting) over every instance whose window is full, then each instance's read-back,
@@ -163,6 +184,7 @@ class PhotometricBundleAdjustment {
   Image_<float> _saliency_map;
   Mat33 _K_inv;
   pba_engine* _engine = nullptr;
+  pba_engine* _track_engine = nullptr;                          // trackFrame's own (2 slots), created at its first call
   // set by the pyramid class when it has already put the next frame into the engine's ring slot on the device
   // (pba_set_frame_pyr_down): addFrame() then skips its own upload
   bool _frame_resident = false;

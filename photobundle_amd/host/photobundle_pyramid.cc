@@ -146,3 +146,19 @@ void PhotometricBundleAdjustmentPyr::addFrame(const uint8_t* image, const float*
   }
   if (result) *result = last;
 }
+
+Mat44 PhotometricBundleAdjustmentPyr::trackFrame(const uint8_t* image, const Mat44& T_init, const TrackOptions& options, TrackResult* result) {
+  const int n = (int)_pyr.size();
+  std::vector<std::vector<uint8_t>> im(n);       // (local: the buffers of addFrame stay as they are)
+  im[0].assign(image, image + (size_t)_rows * _cols);
+  for (int i = 1; i < n; ++i) pyrDownU8(im[i - 1].data(), _sizes[i - 1].rows, _sizes[i - 1].cols, im[i]);
+  Mat44 T(T_init);
+  TrackResult last;
+  for (int i = n - 1; i >= 0; --i) {
+    TrackResult tmp;
+    T = _pyr[i]->trackFrame(im[i].data(), T, options, &tmp);
+    if (i == 0) last = tmp;
+  }
+  if (result) *result = last;
+  return T;
+}

@@ -31,6 +31,11 @@ class PhotometricBundleAdjustmentPyr {
 
   void addFrame(const uint8_t* image, const float* depth_map, const Mat44& T, Result* = nullptr);
 
+  // PhotometricBundleAdjustment::trackFrame coarse to fine: every level aligns its own image (pyrDownU8 of the finer one) to its own
+  // scene points, the result of a level starts the next finer one; the finest level's result is returned.  A level with too few
+  // points hands its start pose on unchanged.
+  Mat44 trackFrame(const uint8_t* image, const Mat44& T_init, const TrackOptions& options = TrackOptions(), TrackResult* result = nullptr);
+
   int numLevels() const { return (int)_pyr.size(); }
 
  private:
