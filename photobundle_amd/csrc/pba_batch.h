@@ -54,18 +54,9 @@ __global__ __launch_bounds__(kTile, 2) void k_schur_batch(const BatchLaunch L) {
   const int b0 = L.begin[k], lb = (int)blockIdx.x - b0, lgrid = L.begin[k + 1] - b0;
   const int mode = L.mode[k];
   SchurParams p = L.tab[L.win[k]].schur[mode & 1];
-  p.dbg = nullptr;
   p.init_scale = (mode >> 1) & 1;
   p.pub_seq = L.seq[k] - 1;
-  if (p.pub_host_seq && lb == 0)
-    lm_publish(p.lm, p.pub_state, p.pub_scal, p.pub_host_scal, p.pub_host_seq, p.pub_seq, threadIdx.x, kTile);
-  if (p.lm) {
-    if (p.lm->done && !p.final_pass) return;
-    if (p.final_pass && !lm_final_pass_needed(p.lm)) return;
-    if (p.lm->cur != p.enq_cur) { p.xyz = p.xyz_alt; p.geom = p.geom_alt; p.rec = p.rec_alt; }
-    p.radius = p.lm->radius;
-    p.inv_radius = 1.0 / p.radius;
-  }
+  if (!schur_prologue(p, false, lb, (int)threadIdx.x)) return;
   __shared__ __attribute__((aligned(16))) char smem[kSchurSmemBytes];
   schur_body<const void>(p, smem, (int)threadIdx.x, lb, lgrid, nullptr, nullptr, true);
 }
@@ -90,11 +81,8 @@ void k_sample_batch(const BatchLaunch L) {
   const int b0 = L.begin[k], lb = (int)blockIdx.x - b0, lgrid = L.begin[k + 1] - b0;
   const int mode = L.mode[k];
   SampleParams p = L.tab[L.win[k]].sample[mode & 1];
-  p.dbg = nullptr;
   if (mode & 1) p.seq = L.seq[k];
-  if (!fused_resolve_parity(p)) return;
-  if (p.lm_init_dst && lb == 0 && threadIdx.x < sizeof(LmState) / 4)      // (as in k_sample)
-    reinterpret_cast<unsigned*>(p.lm_init_dst)[threadIdx.x] = __hip_atomic_load(reinterpret_cast<const unsigned*>(p.lm_init_src) + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (!sample_prologue<true>(p, false, lb, (int)threadIdx.x)) return;
   __shared__ SampleSmem<R, kBatchSampleWaves> sm;
   ResLane<R> unused;
   sample_wg<R, true, kBatchSampleWaves, true, UNITW, false, false, kMaxFrames, true>(p, sm, unused, xcd_logical_block(lb, lgrid), lgrid, (int)threadIdx.x);
@@ -107,11 +95,8 @@ __global__ __launch_bounds__(kBatchSampleWaves * 64) __attribute__((amdgpu_waves
   const int mode = L.mode[k];
   const BatchWindow& bw = L.tab[L.win[k]];
   SampleParams p = bw.sample[mode & 1];
-  p.dbg = nullptr;
   if (mode & 1) p.seq = L.seq[k];
-  if (!fused_resolve_parity(p)) return;
-  if (p.lm_init_dst && lb == 0 && threadIdx.x < sizeof(LmState) / 4)      // (as in k_sample_mc)
-    reinterpret_cast<unsigned*>(p.lm_init_dst)[threadIdx.x] = __hip_atomic_load(reinterpret_cast<const unsigned*>(p.lm_init_src) + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (!sample_prologue<true>(p, false, lb, (int)threadIdx.x)) return;
   sample_mc_wg<R, true, kBatchSampleWaves, true, UNITW>(p, bw.frames_mc, bw.channels, lb, lgrid, (int)threadIdx.x);
 }
 

@@ -615,6 +615,104 @@ int exchange_step_scalars(pba_engine* e, bool packed) {
   return PBA_OK;
 }
 
+// the sequence number behind the scalars of the host mirror, at its device-visible address
+unsigned long long* host_seq_dev(const pba_engine* e) { return reinterpret_cast<unsigned long long*>(e->h_scal_dev + kNumScal); }
+
+// k_schur at the engine's buffers of parity `cur`: everything but what the device decides (async_schur_params adds that)
+SchurParams schur_params(pba_engine* e, int cur, int init_scale, const pba_solver_options* o, double radius) {
+  SchurParams sc{};
+  sc.xyz = e->d_xyz[cur]; sc.rays = e->inverse_depth ? e->d_rays : nullptr; sc.geom = e->d_geom[cur]; sc.rec = e->d_rec[cur]; sc.obs_point = e->d_obs_point;
+  sc.obs_slot = e->d_obs_slot; sc.tile_info = e->d_tile_info; sc.lane_rec = e->d_lane_rec; sc.sp = e->d_sp;
+  sc.ptrec = e->d_ptrec; sc.partial = e->d_partial; sc.rec_stride = e->rec_stride; sc.n_tiles = e->n_tiles; sc.n_frames = e->n_frames;
+  sc.n_free = e->n_free; sc.n_pairs = e->n_pairs; sc.part_stride = e->part_stride; sc.init_scale = init_scale;
+  sc.jacobi = o->jacobi_scaling; sc.fx = e->cfg.fx; sc.fy = e->cfg.fy; sc.radius = radius; sc.inv_radius = 1.0 / radius;
+  sc.min_diag = o->min_lm_diagonal; sc.max_diag = o->max_lm_diagonal;
+  return sc;
+}
+// the reduced solve at parity `cur`, likewise (with_cand: it also forms the candidate cameras' geometry for the fused sampling pass)
+SolveParams solve_params(pba_engine* e, int cur, int init_scale, const pba_solver_options* o, double radius, bool with_cand) {
+  const int cand = 1 - cur;
+  SolveParams so{};
+  so.packed = e->d_packed; so.cams = e->d_cams[cur]; so.cams_cand = e->d_cams[cand]; so.delta_c = e->d_delta_c;
+  so.sc = e->d_sc; so.S_dbg = (e->cfg.flags & 1) ? e->d_S : nullptr; so.rhs_dbg = e->d_rhs; so.scal = e->d_scal; so.geom = e->d_geom[cur];
+  so.n_frames = e->n_frames; so.n_free = e->n_free; so.n_pairs = e->n_pairs; so.stride = e->part_stride; so.fixed_slot = e->fixed_slot; so.tab = e->d_solve_tab;
+  so.geom_cand = with_cand ? e->d_geom[cand] : nullptr;
+  so.init_scale = init_scale; so.jacobi = o->jacobi_scaling; so.radius = radius; so.min_diag = o->min_lm_diagonal; so.max_diag = o->max_lm_diagonal;
+  return so;
+}
+// multi-rank: the fused sampling kernel's last workgroup packs the step scalars into the exchange buffer (the peer mailbox slot, or d_xchg)
+int set_sample_exchange(pba_engine* e, SampleParams& sp) {
+  const int rc = ensure_xchg(e);
+  if (rc) return rc;
+  sp.xchg = e->comm.peer ? peer_slot(e, 1) : e->d_xchg; sp.xchg_sys = e->comm.peer ? 1 : 0;
+  sp.xchg_rank = e->comm.rank; sp.xchg_world = e->comm.world;
+  return PBA_OK;
+}
+
+// ---- phase-timing dumps of the host-stepped driver (PBA_SCHUR_TIMING with a TIMING=1 build) -----------------------------------------
+void dump_schur_phase_cycles(pba_engine* e) {
+  std::vector<unsigned long long> h(8 * (size_t)e->schur_grid);
+  (void)hipMemcpyAsync(h.data(), e->d_dbg, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, e->stream);
+  (void)hipStreamSynchronize(e->stream);
+  double avg[8] = {0};
+  for (int b = 0; b < e->schur_grid; ++b) for (int k = 0; k < 8; ++k) avg[k] += (double)h[8 * b + k] / e->schur_grid;
+  std::fprintf(stderr, "k_schur phase cycles/block (stage, P1, point totals, P + camera record, camera sums, W|Y write, pair blocks): %.0f %.0f %.0f %.0f %.0f %.0f %.0f  tiles/block %.2f\n",
+               avg[0], avg[1], avg[2], avg[3], avg[4], avg[5], avg[6], (double)e->n_tiles / e->schur_grid);
+  {
+    const int rem = e->n_tiles % e->schur_grid;   // blocks [0, rem) run one tile more than the others
+    double d_long = 0, d_short = 0, d_max = 0; int n_long = 0, n_short = 0;
+    for (int b = 0; b < e->schur_grid; ++b) {
+      const double d = 0.01 * (double)h[8 * b + 7];
+      d_max = std::max(d_max, d);
+      if (b < rem) { d_long += d; ++n_long; } else { d_short += d; ++n_short; }
+    }
+    std::fprintf(stderr, "  k_schur tile loop: %d blocks with the extra tile %.2f us, %d others %.2f us, max %.2f us\n", n_long,
+                 n_long ? d_long / n_long : 0.0, n_short, n_short ? d_short / n_short : 0.0, d_max);
+  }
+}
+void dump_fused_sample_timeline(pba_engine* e, const unsigned long long* dbg) {
+  const int fl = e->fused_grid;
+  std::vector<unsigned long long> h(8 * (size_t)fl + 8);
+  (void)hipMemcpyAsync(h.data(), dbg, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, e->stream);
+  (void)hipStreamSynchronize(e->stream);
+  double avg[8] = {0};
+  for (int b = 0; b < fl; ++b) for (int k = 0; k < 6; ++k) avg[k] += (double)(h[8 * b + k] & 0xffffffffffffffull) / fl;
+  // per-XCD timeline (the counters of different XCDs are not assumed to be synchronised)
+  {
+    unsigned long long g0 = ~0ull, g1 = 0;
+    for (int b = 0; b < fl; ++b) { g0 = std::min(g0, h[8 * b + 6]); g1 = std::max(g1, h[8 * b + 7]); }
+    double mean_dur = 0.0;
+    for (int b = 0; b < fl; ++b) mean_dur += 0.01 * (double)(h[8 * b + 7] - h[8 * b + 6]) / fl;
+    std::fprintf(stderr, "k_sample(fused) timeline: first start -> last end %.2f us, mean block duration %.2f us\n",
+                 0.01 * (double)(g1 - g0), mean_dur);
+    int hist[16] = {0};
+    for (int b = 0; b < fl; ++b) { int k = (int)((h[8 * b + 6] - g0) / 400); hist[k > 15 ? 15 : k]++; }
+    const unsigned long long* hf = &h[8 * (size_t)fl];
+    std::fprintf(stderr, "  last workgroup: own work %.2f us, finalisation %.2f us (loads %.2f, reduce %.2f, decide %.2f)\n",
+                 0.01 * (double)hf[1], 0.01 * (double)hf[0], 0.01 * (double)hf[2], 0.01 * (double)hf[3], 0.01 * (double)hf[4]);
+    std::fprintf(stderr, "  block starts per 4 us bin:");
+    for (int k = 0; k < 16; ++k) std::fprintf(stderr, " %d", hist[k]);
+    std::fprintf(stderr, "\n");
+  }
+  for (int x = 0; x < 8; ++x) {
+    unsigned long long t0 = ~0ull, t1 = 0; int n = 0; int late = 0;
+    int mism = 0;
+    for (int b = 0; b < fl; ++b) {
+      if ((int)(h[8 * b] >> 56) != x) continue;
+      t0 = std::min(t0, h[8 * b + 6]); t1 = std::max(t1, h[8 * b + 7]); ++n;
+      if ((b & 7) != x) ++mism;
+    }
+    unsigned long long first_end = ~0ull;
+    for (int b = 0; b < fl; ++b) if ((int)(h[8 * b] >> 56) == x) first_end = std::min(first_end, h[8 * b + 7]);
+    for (int b = 0; b < fl; ++b) if ((int)(h[8 * b] >> 56) == x && h[8 * b + 6] >= first_end) ++late;
+    (void)mism;
+    std::fprintf(stderr, "  xcd %d: %d blocks, span %.2f us, first block done after %.2f us, %d blocks started later than that\n",
+                 x, n, 0.01 * (double)(t1 - t0), 0.01 * (double)(first_end - t0), late);
+  }
+  std::fprintf(stderr, "k_sample(fused) phase cycles/block: geom-stage %.0f  backsub %.0f  geometry+base %.0f  staging %.0f  walk %.0f  loss+reduce %.0f\n",
+               avg[0], avg[1], avg[2], avg[3], avg[4], avg[5]);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1538,7 +1636,7 @@ static int pose_step(pba_engine* e, double radius, int32_t init_scale, const pba
   HIP_TRY(e, hipGetLastError());
   e->pose_sums_cur = cur;
   const unsigned long long seq = ++e->seq;
-  unsigned long long* h_seq_dev = reinterpret_cast<unsigned long long*>(e->h_scal_dev + kNumScal);
+  unsigned long long* const h_seq_dev = host_seq_dev(e);
   if (!grad_only) {
     // candidate point: Jacobian pass when speculating on acceptance, else cost pass; the points are the current ones
     SampleParams sp = make_sample_params(e, cand);
@@ -1581,14 +1679,7 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
   const int n = 6 * e->n_free;
   const bool multi = e->comm.multi();
 
-  SchurParams sc{};
-  sc.xyz = e->d_xyz[cur]; sc.rays = e->inverse_depth ? e->d_rays : nullptr; sc.geom = e->d_geom[cur]; sc.rec = e->d_rec[cur]; sc.obs_point = e->d_obs_point;
-  sc.obs_slot = e->d_obs_slot; sc.tile_info = e->d_tile_info; sc.lane_rec = e->d_lane_rec; sc.sp = e->d_sp;
-  sc.ptrec = e->d_ptrec; sc.partial = e->d_partial; sc.rec_stride = e->rec_stride; sc.n_tiles = e->n_tiles; sc.n_frames = e->n_frames;
-  sc.n_free = e->n_free; sc.n_pairs = e->n_pairs; sc.part_stride = e->part_stride; sc.init_scale = init_scale;
-  sc.jacobi = o->jacobi_scaling; sc.fx = e->cfg.fx; sc.fy = e->cfg.fy; sc.radius = radius; sc.inv_radius = 1.0 / radius;
-  sc.min_diag = o->min_lm_diagonal; sc.max_diag = o->max_lm_diagonal;
-  sc.dbg = nullptr; sc.lm = nullptr;
+  SchurParams sc = schur_params(e, cur, init_scale, o, radius);
   if (e->dbg_left > 0 && !e->wide) {
     if (!e->d_dbg) { (void)hipMalloc(reinterpret_cast<void**>(&e->d_dbg), sizeof(unsigned long long) * 8 * (1024 + 4096)); }
     sc.dbg = e->d_dbg;
@@ -1601,37 +1692,8 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
     launch_schur(e, sc);
     ev_end(e, 2);
   }
-  if (sc.dbg) {
-    std::vector<unsigned long long> h(8 * (size_t)e->schur_grid);
-    (void)hipMemcpyAsync(h.data(), e->d_dbg, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, e->stream);
-    (void)hipStreamSynchronize(e->stream);
-    double avg[8] = {0};
-    for (int b = 0; b < e->schur_grid; ++b) for (int k = 0; k < 8; ++k) avg[k] += (double)h[8 * b + k] / e->schur_grid;
-    std::fprintf(stderr, "k_schur phase cycles/block (stage, P1, point totals, P + camera record, camera sums, W|Y write, pair blocks): %.0f %.0f %.0f %.0f %.0f %.0f %.0f  tiles/block %.2f\n",
-                 avg[0], avg[1], avg[2], avg[3], avg[4], avg[5], avg[6], (double)e->n_tiles / e->schur_grid);
-    {
-      const int rem = e->n_tiles % e->schur_grid;   // blocks [0, rem) run one tile more than the others
-      double d_long = 0, d_short = 0, d_max = 0; int n_long = 0, n_short = 0;
-      for (int b = 0; b < e->schur_grid; ++b) {
-        const double d = 0.01 * (double)h[8 * b + 7];
-        d_max = std::max(d_max, d);
-        if (b < rem) { d_long += d; ++n_long; } else { d_short += d; ++n_short; }
-      }
-      std::fprintf(stderr, "  k_schur tile loop: %d blocks with the extra tile %.2f us, %d others %.2f us, max %.2f us\n", n_long,
-                   n_long ? d_long / n_long : 0.0, n_short, n_short ? d_short / n_short : 0.0, d_max);
-    }
-    --e->dbg_left;
-  }
-  SolveParams so{};
-  so.packed = e->d_packed;
-  so.cams = e->d_cams[cur]; so.cams_cand = e->d_cams[cand]; so.delta_c = e->d_delta_c;
-  so.sc = e->d_sc; so.S_dbg = (e->cfg.flags & 1) ? e->d_S : nullptr; so.rhs_dbg = e->d_rhs; so.scal = e->d_scal; so.geom = e->d_geom[cur];
-  so.n_frames = e->n_frames; so.n_free = e->n_free; so.n_pairs = e->n_pairs; so.stride = e->part_stride;
-  so.fixed_slot = e->fixed_slot; so.tab = e->d_solve_tab;
-  so.geom_cand = (!grad_only && fused_capable(e)) ? e->d_geom[cand] : nullptr;
-  so.init_scale = init_scale; so.jacobi = o->jacobi_scaling; so.radius = radius; so.min_diag = o->min_lm_diagonal;
-  so.max_diag = o->max_lm_diagonal;
-  so.lm = nullptr;
+  if (sc.dbg) { dump_schur_phase_cycles(e); --e->dbg_left; }
+  SolveParams so = solve_params(e, cur, init_scale, o, radius, !grad_only && fused_capable(e));
   so.dbg = (e->dbg_left > 0) ? 1 : 0;
   if (e->wide) {
     ev_begin(e, 3);
@@ -1643,7 +1705,7 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
     if (rcs) return rcs;
   }
   const unsigned long long seq = ++e->seq;
-  unsigned long long* h_seq_dev = reinterpret_cast<unsigned long long*>(e->h_scal_dev + kNumScal);
+  unsigned long long* const h_seq_dev = host_seq_dev(e);
   bool xchg_packed = false;
   if (!grad_only && fused_capable(e)) {
     // one kernel: back-substitution -> candidate pass (Jacobian pass when speculating) -> step finalisation
@@ -1654,10 +1716,9 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
     sp.host_scal = multi ? nullptr : e->h_scal_dev; sp.host_seq = h_seq_dev; sp.seq = seq; sp.n_tiles = e->n_tiles;
     sp.dbg = (e->dbg_left > 0 && e->d_dbg) ? e->d_dbg + 8 * 1024 : nullptr;
     if (multi) {
-      int rcx = ensure_xchg(e);
+      const int rcx = set_sample_exchange(e, sp);
       if (rcx) return rcx;
-      sp.xchg = e->comm.peer ? peer_slot(e, 1) : e->d_xchg; sp.xchg_sys = e->comm.peer ? 1 : 0;
-      sp.xchg_rank = e->comm.rank; sp.xchg_world = e->comm.world; xchg_packed = true;
+      xchg_packed = true;
     }
     if (e->speculate) {
       ev_begin(e, 0);
@@ -1672,48 +1733,7 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
     }
     e->cost_blocks[cand] = e->fused_grid;
     e->lin_valid[cand] = e->speculate;
-    if (sp.dbg) {
-      const int fl = e->fused_grid;
-      std::vector<unsigned long long> h(8 * (size_t)fl + 8);
-      (void)hipMemcpyAsync(h.data(), sp.dbg, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, e->stream);
-      (void)hipStreamSynchronize(e->stream);
-      double avg[8] = {0};
-      for (int b = 0; b < fl; ++b) for (int k = 0; k < 6; ++k) avg[k] += (double)(h[8 * b + k] & 0xffffffffffffffull) / fl;
-      // per-XCD timeline (the counters of different XCDs are not assumed to be synchronised)
-      {
-        unsigned long long g0 = ~0ull, g1 = 0;
-        for (int b = 0; b < fl; ++b) { g0 = std::min(g0, h[8 * b + 6]); g1 = std::max(g1, h[8 * b + 7]); }
-        double mean_dur = 0.0;
-        for (int b = 0; b < fl; ++b) mean_dur += 0.01 * (double)(h[8 * b + 7] - h[8 * b + 6]) / fl;
-        std::fprintf(stderr, "k_sample(fused) timeline: first start -> last end %.2f us, mean block duration %.2f us\n",
-                     0.01 * (double)(g1 - g0), mean_dur);
-        int hist[16] = {0};
-        for (int b = 0; b < fl; ++b) { int k = (int)((h[8 * b + 6] - g0) / 400); hist[k > 15 ? 15 : k]++; }
-        const unsigned long long* hf = &h[8 * (size_t)fl];
-        std::fprintf(stderr, "  last workgroup: own work %.2f us, finalisation %.2f us (loads %.2f, reduce %.2f, decide %.2f)\n",
-                     0.01 * (double)hf[1], 0.01 * (double)hf[0], 0.01 * (double)hf[2], 0.01 * (double)hf[3], 0.01 * (double)hf[4]);
-        std::fprintf(stderr, "  block starts per 4 us bin:");
-        for (int k = 0; k < 16; ++k) std::fprintf(stderr, " %d", hist[k]);
-        std::fprintf(stderr, "\n");
-      }
-      for (int x = 0; x < 8; ++x) {
-        unsigned long long t0 = ~0ull, t1 = 0; int n = 0; int late = 0;
-        int mism = 0;
-        for (int b = 0; b < fl; ++b) {
-          if ((int)(h[8 * b] >> 56) != x) continue;
-          t0 = std::min(t0, h[8 * b + 6]); t1 = std::max(t1, h[8 * b + 7]); ++n;
-          if ((b & 7) != x) ++mism;
-        }
-        unsigned long long first_end = ~0ull;
-        for (int b = 0; b < fl; ++b) if ((int)(h[8 * b] >> 56) == x) first_end = std::min(first_end, h[8 * b + 7]);
-        for (int b = 0; b < fl; ++b) if ((int)(h[8 * b] >> 56) == x && h[8 * b + 6] >= first_end) ++late;
-        (void)mism;
-        std::fprintf(stderr, "  xcd %d: %d blocks, span %.2f us, first block done after %.2f us, %d blocks started later than that\n",
-                     x, n, 0.01 * (double)(t1 - t0), 0.01 * (double)(first_end - t0), late);
-      }
-      std::fprintf(stderr, "k_sample(fused) phase cycles/block: geom-stage %.0f  backsub %.0f  geometry+base %.0f  staging %.0f  walk %.0f  loss+reduce %.0f\n",
-                   avg[0], avg[1], avg[2], avg[3], avg[4], avg[5]);
-    }
+    if (sp.dbg) dump_fused_sample_timeline(e, sp.dbg);
   } else if (!grad_only) {
     BacksubParams bs{};
     bs.xyz = e->d_xyz[cur]; bs.rays = e->inverse_depth ? e->d_rays : nullptr; bs.xyz_cand = e->d_xyz[cand]; bs.geom = e->d_geom[cur]; bs.rec = e->d_rec[cur];
@@ -2002,7 +2022,7 @@ namespace {
 SampleParams async_sample_params(pba_engine* e, int kind) {
   const int cur = e->async_cur, cand = 1 - cur;
   const bool skip = kind == 0;
-  unsigned long long* h_seq_dev = reinterpret_cast<unsigned long long*>(e->h_scal_dev + kNumScal);
+  unsigned long long* const h_seq_dev = host_seq_dev(e);
   SampleParams sp = make_sample_params(e, skip ? cur : cand);
   sp.tile_info = e->d_tile_info; sp.lane_rec = e->d_lane_rec;
   sp.geom_prev = e->d_geom[skip ? cand : cur]; sp.xyz_prev = e->d_xyz[skip ? cand : cur]; sp.rec_prev = e->d_rec[skip ? cand : cur];
@@ -2023,29 +2043,17 @@ SampleParams async_sample_params(pba_engine* e, int kind) {
 // k_schur of kind 1 (full iteration) / 2 (gradient norms of the final point); pub_seq = the engine's last sequence number, no stamps
 SchurParams async_schur_params(pba_engine* e, int kind, int init_scale, const pba_solver_options* o) {
   const int cur = e->async_cur, cand = 1 - cur;
-  SchurParams sc{};
-  sc.xyz = e->d_xyz[cur]; sc.rays = e->inverse_depth ? e->d_rays : nullptr; sc.geom = e->d_geom[cur]; sc.rec = e->d_rec[cur]; sc.obs_point = e->d_obs_point;
-  sc.obs_slot = e->d_obs_slot; sc.tile_info = e->d_tile_info; sc.lane_rec = e->d_lane_rec; sc.sp = e->d_sp;
-  sc.ptrec = e->d_ptrec; sc.partial = e->d_partial; sc.rec_stride = e->rec_stride; sc.n_tiles = e->n_tiles; sc.n_frames = e->n_frames;
-  sc.n_free = e->n_free; sc.n_pairs = e->n_pairs; sc.part_stride = e->part_stride; sc.init_scale = init_scale;
+  SchurParams sc = schur_params(e, cur, init_scale, o, 1.0);      // (the radius comes from the device state)
   // the previous enqueue decided on the device (last workgroup of the fused sampling kernel, or k_decide after the
   // multi-rank exchange) without publishing; this kernel does
   sc.pub_state = e->h_lm_dev; sc.pub_scal = e->d_scal; sc.pub_host_scal = e->h_scal_dev;
-  sc.pub_host_seq = reinterpret_cast<unsigned long long*>(e->h_scal_dev + kNumScal); sc.pub_seq = e->seq;
-  sc.jacobi = o->jacobi_scaling; sc.fx = e->cfg.fx; sc.fy = e->cfg.fy; sc.radius = 1.0; sc.inv_radius = 1.0;
-  sc.min_diag = o->min_lm_diagonal; sc.max_diag = o->max_lm_diagonal; sc.dbg = nullptr;
-  sc.stamp = nullptr;
+  sc.pub_host_seq = host_seq_dev(e); sc.pub_seq = e->seq;
   sc.lm = e->d_lm; sc.enq_cur = cur; sc.final_pass = (kind == 2) ? 1 : 0; sc.xyz_alt = e->d_xyz[cand]; sc.geom_alt = e->d_geom[cand]; sc.rec_alt = e->d_rec[cand];
   return sc;
 }
 SolveParams async_solve_params(pba_engine* e, int kind, int init_scale, const pba_solver_options* o) {
   const int cur = e->async_cur, cand = 1 - cur;
-  SolveParams so{};
-  so.packed = e->d_packed; so.cams = e->d_cams[cur]; so.cams_cand = e->d_cams[cand]; so.delta_c = e->d_delta_c;
-  so.sc = e->d_sc; so.S_dbg = (e->cfg.flags & 1) ? e->d_S : nullptr; so.rhs_dbg = e->d_rhs; so.scal = e->d_scal; so.geom = e->d_geom[cur];
-  so.n_frames = e->n_frames; so.n_free = e->n_free; so.n_pairs = e->n_pairs; so.stride = e->part_stride; so.fixed_slot = e->fixed_slot; so.tab = e->d_solve_tab;
-  so.geom_cand = (kind == 1) ? e->d_geom[cand] : nullptr;
-  so.init_scale = init_scale; so.jacobi = o->jacobi_scaling; so.radius = 1.0; so.min_diag = o->min_lm_diagonal; so.max_diag = o->max_lm_diagonal;
+  SolveParams so = solve_params(e, cur, init_scale, o, 1.0, kind == 1);
   so.lm = e->d_lm; so.enq_cur = cur; so.final_pass = (kind == 2) ? 1 : 0; so.cams_alt = e->d_cams[cand]; so.cams_cand_alt = e->d_cams[cur]; so.geom_alt = e->d_geom[cand];
   so.geom_cand_alt = e->d_geom[cur];
   return so;
@@ -2054,7 +2062,7 @@ SolveParams async_solve_params(pba_engine* e, int kind, int init_scale, const pb
 ReduceSolveParams::Fin async_fin(pba_engine* e, unsigned long long seq) {
   ReduceSolveParams::Fin fin{};
   fin.lm = e->d_lm; fin.log = e->d_log; fin.host_log = e->h_log_dev; fin.max_log = (int)pba_engine::kMaxLog; fin.host_state = e->h_lm_dev;
-  fin.host_scal = e->h_scal_dev; fin.host_seq = reinterpret_cast<unsigned long long*>(e->h_scal_dev + kNumScal); fin.seq = seq;
+  fin.host_scal = e->h_scal_dev; fin.host_seq = host_seq_dev(e); fin.seq = seq;
   return fin;
 }
 }  // namespace
@@ -2067,7 +2075,7 @@ int pba_internal_async_enqueue(pba_engine* e, int kind, int init_scale, const pb
   const int cur = e->async_cur, cand = 1 - cur;
   const int n = 6 * e->n_free;
   const bool multi = e->comm.multi();
-  unsigned long long* h_seq_dev = reinterpret_cast<unsigned long long*>(e->h_scal_dev + kNumScal);
+  unsigned long long* const h_seq_dev = host_seq_dev(e);
   *seq_out = 0;
   if (kind == 0) {
     // plain Jacobian pass at the current point, on the fused (tile) grid so that both parities share one block count
@@ -2107,10 +2115,8 @@ int pba_internal_async_enqueue(pba_engine* e, int kind, int init_scale, const pb
     sp.stamp = stamp_record(e);
     sp.seq = seq;
     if (multi) {
-      int rcx = ensure_xchg(e);
+      const int rcx = set_sample_exchange(e, sp);
       if (rcx) return rcx;
-      sp.xchg = e->comm.peer ? peer_slot(e, 1) : e->d_xchg; sp.xchg_sys = e->comm.peer ? 1 : 0;
-      sp.xchg_rank = e->comm.rank; sp.xchg_world = e->comm.world;
       if (e->comm.peer) {
         // the exchange of the step scalars has no kernel of its own: the sampling kernel's last workgroup raises the flag,
         // k_decide waits for every rank's and sums the slots
@@ -2297,7 +2303,7 @@ int pba_internal_resident_launch(pba_engine* e, const pba_solver_options* o, uns
   // every device-side wait is bounded (a lost flag must not hang the GPU): well below the host watchdog and the compute-queue's own
   P.timeout_ticks = (unsigned long long)(std::min(2.0, 0.25 * e->wait_timeout_s) * e->tick_hz);
   P.lm_init = e->h_lm_dev; P.host_state = e->h_lm_dev; P.log = e->d_log; P.host_log = e->h_log_dev; P.max_log = (int)pba_engine::kMaxLog;
-  P.host_scal = e->h_scal_dev; P.host_seq = reinterpret_cast<unsigned long long*>(e->h_scal_dev + kNumScal);
+  P.host_scal = e->h_scal_dev; P.host_seq = host_seq_dev(e);
   const unsigned long long seq = ++e->seq;
   P.seq = seq;
   P.stamp = nullptr;

@@ -859,6 +859,19 @@ __device__ __forceinline__ bool fused_resolve_parity(SampleParams& p) {
   return true;
 }
 
+// What every sampling launch does first (k_sample, k_sample_mc and their batched forms, pba_batch.h), for workgroup `bid` of its
+// window: the phase stamps are off unless keep_dbg; a fused pass then takes the parity the device decided and leaves when the solve is
+// over (returns false); the first pass of a solve has workgroup 0 copy the initial LM state from the host mirror to the device
+// (consumed by the NEXT kernel of the stream).
+template <bool FUSED>
+__device__ __forceinline__ bool sample_prologue(SampleParams& p, const bool keep_dbg, const int bid, const int tix) {
+  if (!keep_dbg) p.dbg = nullptr;
+  if (FUSED && !fused_resolve_parity(p)) return false;
+  if (FUSED && p.lm_init_dst && bid == 0 && tix < (int)(sizeof(LmState) / 4))
+    reinterpret_cast<unsigned*>(p.lm_init_dst)[tix] = __hip_atomic_load(reinterpret_cast<const unsigned*>(p.lm_init_src) + tix, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  return true;
+}
+
 // whole-point tiles of <= 128 observations, two per 256-thread workgroup
 struct FusedIdx { int4 ti; int pt, slot, l0, cnt; };
 template <int NT>
@@ -1120,7 +1133,7 @@ __device__ __forceinline__ void fused_sum_partials(const double* block_bs, const
 template <int WAVES>
 // n_grid_in: workgroups of the window (the batched launches, pba_batch.h), < 0 = the grid of the launch
 __device__ __forceinline__ void fused_finalize(const SampleParams& p, int lane, int wave, int* s_f, double* s_r4, unsigned long long t_begin, const int tix,
-                                               const int n_grid_in = -1) {
+                                               const int n_grid_in) {
   constexpr int NTH = WAVES * 64;
   const unsigned n_grid = n_grid_in < 0 ? gridDim.x : (unsigned)n_grid_in;
   __shared__ int s_last;
@@ -1851,10 +1864,7 @@ template <int R, bool JAC, int WAVES, bool FUSED, bool UNITW, bool FAST, int MF 
 __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu((R <= 2 ? (JAC ? PBA_SAMPLE_WAVES_PER_SIMD : 2) : (R >= 4 ? PBA_SAMPLE_WAVES_LARGE : 2)), (R <= 2 ? (JAC ? PBA_SAMPLE_WAVES_PER_SIMD : 2) : (R >= 4 ? PBA_SAMPLE_WAVES_LARGE : 2)))))
 void k_sample(SampleParams p_in) {
   SampleParams p = p_in;
-  if (!PBA_PHASE_TIMING) p.dbg = nullptr;
-  if (FUSED && !fused_resolve_parity(p)) return;
-  if (FUSED && p.lm_init_dst && blockIdx.x == 0 && threadIdx.x < sizeof(LmState) / 4)      // (consumed by the NEXT kernel of the stream)
-    reinterpret_cast<unsigned*>(p.lm_init_dst)[threadIdx.x] = __hip_atomic_load(reinterpret_cast<const unsigned*>(p.lm_init_src) + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (!sample_prologue<FUSED>(p, PBA_PHASE_TIMING != 0, (int)blockIdx.x, (int)threadIdx.x)) return;
   __shared__ SampleSmem<R, WAVES, MF> sm;
   ResLane<R> unused;      // (three-kernel path: nothing is resident)
   sample_wg<R, JAC, WAVES, FUSED, UNITW, FAST, false, MF>(p, sm, unused, xcd_logical_block(blockIdx.x, gridDim.x), (int)gridDim.x, (int)threadIdx.x);
@@ -2076,8 +2086,8 @@ constexpr int sample_mc_rows_per_batch(int R) { return R == 2 ? PBA_MC_RB2 : (((
 //   FUSED: like k_sample's fused form -- back-substitution of the step for the workgroup's whole points first, sampling at
 //   the candidate it just formed, step finalisation (and, single rank, the trust-region decision) by the last workgroup.
 //   UNITW: unit patch weights (MakePatchWeights without the Gaussian, the reference's default): w^2 = 1 is folded away.
-// k_sample_mc's body for workgroup `bid` of `n_blocks` (tix = threadIdx.x): what the batched launch (pba_batch.h) runs per window.  The
-// solo kernel after it keeps its own copy of these lines (its code generation stays as measured): an edit to one belongs in both.
+// k_sample_mc's body for workgroup `bid` of `n_blocks` (tix = threadIdx.x): the solo kernel after it runs it with the launch's own block
+// and grid, the batched launch (pba_batch.h) with the window's.
 template <int R, bool JAC, int WAVES, bool FUSED, bool UNITW, int MF = kMaxFrames>
 __device__ __forceinline__ void sample_mc_wg(SampleParams& p, const float* __restrict__ frames_mc, int n_channels, const int bid, const int n_blocks,
                                              const int tix) {
@@ -2305,232 +2315,9 @@ __device__ __forceinline__ void sample_mc_wg(SampleParams& p, const float* __res
 
 template <int R, bool JAC, int WAVES, bool FUSED, bool UNITW, int MF = kMaxFrames>
 __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(PBA_MC_WAVES(R), PBA_MC_WAVES(R)))) void k_sample_mc(SampleParams p_in, const float* __restrict__ frames_mc, int n_channels) {
-  static_assert(!FUSED || (WAVES * 64) % 128 == 0, "fused tiles are 128 observations");
-  static_assert(MF == kMaxFrames || !FUSED, "the wide-window tables (MF > kMaxFrames) are for the unfused chain");
   SampleParams p = p_in;
-  p.dbg = nullptr;
-  if (FUSED && !fused_resolve_parity(p)) return;
-  if (FUSED && p.lm_init_dst && blockIdx.x == 0 && threadIdx.x < sizeof(LmState) / 4)      // (as in k_sample)
-    reinterpret_cast<unsigned*>(p.lm_init_dst)[threadIdx.x] = __hip_atomic_load(reinterpret_cast<const unsigned*>(p.lm_init_src) + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  constexpr int W = 2 * R + 1, F = 2 * R + 2;
-  constexpr int H = JAC ? 1 : 0;                    // halo: the gradients of a footprint texel need its four neighbours
-  constexpr int FW = F + 2 * H;                     // staged columns
-  constexpr int RB = sample_mc_rows_per_batch(R);   // footprint rows per batch
-  constexpr int SR = RB + 2 * H;                    // staged rows per batch
-  constexpr int NB = (F + RB - 1) / RB;
-  constexpr int FF = SR * FW;
-  constexpr int LSTRIDE = 65;
-  constexpr int NPL = JAC ? 3 : 1;
-  constexpr size_t kTexBytes = sizeof(float) * WAVES * FF * LSTRIDE;
-  constexpr size_t kBsBytes = FUSED ? sizeof(double) * 3 * WAVES * 64 : 0;      // back-substitution scratch ahead of the tables
-  constexpr size_t kPreBytes = kBsBytes + (FUSED ? 2 : 1) * MF * sizeof(CamGeom);
-  static_assert(!FUSED || kTexBytes >= sizeof(double) * 4 * WAVES * 64, "the finalisation reuses the texel region");
-  __shared__ __attribute__((aligned(16))) char s_raw[kTexBytes > kPreBytes ? kTexBytes : kPreBytes];
-  float (*s_tex)[FF * LSTRIDE] = reinterpret_cast<float (*)[FF * LSTRIDE]>(s_raw);
-  __shared__ int32_t s_base[WAVES][64];
-  __shared__ double s_red[4 * WAVES];
-  __shared__ int32_t s_fail;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int bid = blockIdx.x;
-  int obs = blockIdx.x * (WAVES * 64) + threadIdx.x;
-  bool active = obs < p.n_obs;
-  if (threadIdx.x == 0) s_fail = 0;
-  CamGeom* s_geom = reinterpret_cast<CamGeom*>(s_raw + kBsBytes);
-  double* s_bk = reinterpret_cast<double*>(s_geom + MF);
-  FusedIdx fi{make_int4(0, 0, 0, 0), 0, 0, 0, 0};
-  if (FUSED) fi = fused_prefetch_indices<WAVES * 64>(p, bid, (int)threadIdx.x);
-  stage_geom<WAVES * 64, false, MF>(p.geom, s_geom, p.n_frames, threadIdx.x);
-  if (FUSED) fused_stage_step_table<WAVES * 64>(p, s_bk, (int)threadIdx.x);
-  lds_barrier();
-
-  int pt = 0, slot = 0;
-  double prm[3] = {0.0, 0.0, 0.0};
-  double bs_mcc = 0.0, bs_st2 = 0.0, bs_x2 = 0.0;
-  if (FUSED) {
-    fused_backsub<WAVES * 64>(p, p.rays, fi, s_bk, reinterpret_cast<double*>(s_raw), pt, slot, obs, active, prm, bs_mcc, bs_st2, bs_x2, (int)threadIdx.x);
-  } else if (active) {
-    pt = p.obs_point[obs];
-    slot = p.obs_slot[obs];
-    prm[0] = p.xyz[3 * (size_t)pt]; prm[1] = p.xyz[3 * (size_t)pt + 1]; prm[2] = p.xyz[3 * (size_t)pt + 2];
-  }
-  double u = 0.0, v = 0.0;
-  int bx = 0, by = 0;
-  bool regular = false;
-  float dxs[W], dys[W];
-  double omdx[W];
-#pragma unroll
-  for (int j = 0; j < W; ++j) { dxs[j] = 1.f; dys[j] = 1.f; omdx[j] = 0.0; }
-  const size_t npix = (size_t)p.rows * p.cols;
-  if (active) {
-    if (p.rays && !(prm[0] > 0.0)) atomicOr(&s_fail, 1);     // inverse-depth variant: rho <= 0 is an evaluation failure (k_sample)
-    double X[3], qd[3];
-    point_world(p.rays, pt, prm, X, qd);
-    double xw[3];
-    transform_point(s_geom[slot], X, xw);
-    project_point(xw, p.fx, p.fy, p.cx, p.cy, u, v);
-    float xf[W], yf[W];
-#pragma unroll
-    for (int j = 0; j < W; ++j) { xf[j] = (float)(u + (double)(j - R)); yf[j] = (float)(v + (double)(j - R)); }
-    bx = trunc_x86(xf[0]);
-    by = trunc_x86(yf[0]);
-    // regular: consecutive taps whose whole footprint is INTERIOR (the gradients of its texels come from a one-pixel halo
-    // of values; the image border, where they are zero by definition, goes to the per-tap path)
-    bool reg = (bx >= 1) && (bx + F <= p.cols - 1) && (by >= 1) && (by + F <= p.rows - 1);
-#pragma unroll
-    for (int j = 1; j < W; ++j) reg = reg && (trunc_x86(xf[j]) == bx + j) && (trunc_x86(yf[j]) == by + j);
-    regular = reg;
-#pragma unroll
-    for (int j = 0; j < W; ++j) {
-      dxs[j] = __fsub_rn((float)(bx + j + 1), xf[j]);
-      dys[j] = __fsub_rn((float)(by + j + 1), yf[j]);
-      omdx[j] = __dsub_rn(1.0, (double)dxs[j]);
-    }
-  }
-  // index of the first staged value (footprint origin minus the halo) in channel 0 of the observation's frame (-1: not staged)
-  s_base[wave][lane] = (active && regular) ? (int32_t)((size_t)slot * n_channels * npix + (size_t)(by - H) * p.cols + (bx - H)) : -1;
-  lds_barrier();      // the camera table is dead from here on: its LDS is reused by the texel batches
-
-  const bool walk = active && regular;
-  double m11 = 0, m12 = 0, m22 = 0, b1 = 0, b2 = 0, cc = 0;
-  constexpr int OPI = 64 / FW;                      // observations per staging pass: lane = (observation, staged column)
-  constexpr int NG = (64 + OPI - 1) / OPI;
-  const int oi = lane / FW, tc = lane - oi * FW;
-#pragma unroll 1
-  for (int k = 0; k < n_channels; ++k) {
-    const float* p0 = p.desc + ((size_t)pt * n_channels + k) * (W * W);
-    double Hp[NPL][W];
-#pragma unroll
-    for (int pl = 0; pl < NPL; ++pl)
-#pragma unroll
-      for (int j = 0; j < W; ++j) Hp[pl][j] = 0.0;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      const int r0 = b * RB;
-      const int nr = (F - r0 < RB) ? F - r0 : RB;
-      wave_lds_sync();                              // the previous batch (or channel) has been walked
-#pragma unroll 1
-      for (int g = 0; g < NG; ++g) {
-        const int o = g * OPI + oi;
-        const int32_t bs = (oi < OPI && o < 64) ? s_base[wave][o & 63] : -1;
-        if (bs >= 0) {
-          const float* src = frames_mc + (size_t)bs + (size_t)k * npix + tc;
-          float tv[SR];
-#pragma unroll
-          for (int sr = 0; sr < SR; ++sr) if (sr < nr + 2 * H) tv[sr] = src[(size_t)(r0 + sr) * p.cols];     // all loads of the pass in flight
-#pragma unroll
-          for (int sr = 0; sr < SR; ++sr) if (sr < nr + 2 * H) s_tex[wave][(sr * FW + tc) * LSTRIDE + o] = tv[sr];
-        }
-      }
-      wave_lds_sync();
-      if (walk) {
-#pragma unroll
-        for (int rr = 0; rr < RB; ++rr) {
-          if (rr >= nr) continue;
-          const int r = r0 + rr, i = r - 1;
-          const float dy = dys[r >= 1 ? i : 0];
-          const float omdy = __fsub_rn(1.0f, dy);
-          __builtin_amdgcn_sched_barrier(0);      // one footprint row at a time: hoisting the LDS reads of later rows costs registers (spills at R = 1, 3, 5)
-          // values of the footprint row (with its left / right halo) and, for the gradients, of the rows above and below
-          float vm[FW], t[NPL][F];
-#pragma unroll
-          for (int c = 0; c < FW; ++c) vm[c] = s_tex[wave][((rr + H) * FW + c) * LSTRIDE + lane];
-#pragma unroll
-          for (int c = 0; c < F; ++c) {
-            t[0][c] = vm[c + H];
-            if (JAC) {
-              const float up = s_tex[wave][(rr * FW + c + H) * LSTRIDE + lane], dn = s_tex[wave][((rr + 2 * H) * FW + c + H) * LSTRIDE + lane];
-              t[NPL > 1 ? 1 : 0][c] = 0.5f * __fsub_rn(vm[c + 2 * H], vm[c]);       // imgproc.cc:27-95 on the channel image
-              t[NPL > 2 ? 2 : 0][c] = 0.5f * __fsub_rn(dn, up);
-            }
-          }
-#pragma unroll
-          for (int j = 0; j < W; ++j) {
-            const double h0 = hlerp_exact(dxs[j], omdx[j], t[0][j], t[0][j + 1]);
-            double h1 = 0.0, h2 = 0.0;
-            if (JAC) {
-              h1 = hlerp_exact(dxs[j], omdx[j], t[NPL > 1 ? 1 : 0][j], t[NPL > 1 ? 1 : 0][j + 1]);
-              h2 = hlerp_exact(dxs[j], omdx[j], t[NPL > 2 ? 2 : 0][j], t[NPL > 2 ? 2 : 0][j + 1]);
-            }
-            if (r >= 1) {
-              const float sI = vlerp_exact(dy, omdy, Hp[0][j], h0);
-              const double e = (double)p0[i * W + j] - (double)sI;
-              const double w2 = UNITW ? 1.0 : p.w2[i * W + j];
-              cc += w2 * e * e;
-              if (JAC) {
-                const double gx = (double)vlerp_exact(dy, omdy, Hp[NPL > 1 ? 1 : 0][j], h1);
-                const double gy = (double)vlerp_exact(dy, omdy, Hp[NPL > 2 ? 2 : 0][j], h2);
-                const double wgx = w2 * gx, wgy = w2 * gy;
-                m11 += wgx * gx; m12 += wgx * gy; m22 += wgy * gy;
-                b1 += wgx * e; b2 += wgy * e;
-              }
-            }
-            Hp[0][j] = h0;
-            if (JAC) { Hp[NPL > 1 ? 1 : 0][j] = h1; Hp[NPL > 2 ? 2 : 0][j] = h2; }
-          }
-        }
-      }
-    }
-    if (active && !regular) {
-      const float* frame = frames_mc + ((size_t)slot * n_channels + k) * npix;
-#pragma unroll 1
-      for (int i = 0; i < W; ++i) {
-        const float yfi = (float)(v + (double)(i - R));
-#pragma unroll 1
-        for (int j = 0; j < W; ++j) {
-          const float xfj = (float)(u + (double)(j - R));
-          float sI, sgx = 0.f, sgy = 0.f;
-          sample_generic_mc<JAC>(frame, p.rows, p.cols, yfi, xfj, sI, sgx, sgy);
-          const double e = (double)p0[i * W + j] - (double)sI;
-          const double w2 = p.w2[i * W + j];
-          cc += w2 * e * e;
-          if (JAC) {
-            const double gx = (double)sgx, gy = (double)sgy;
-            const double wgx = w2 * gx, wgy = w2 * gy;
-            m11 += wgx * gx; m12 += wgx * gy; m22 += wgy * gy;
-            b1 += wgx * e; b2 += wgy * e;
-          }
-        }
-      }
-    }
-  }
-
-  // loss (HuberLoss::Evaluate + Corrector with rho'' <= 0) over the WHOLE block (all channels), record, block cost
-  double cost_obs = 0.0;
-  if (active) {
-    double rho0 = cc, rho1 = 1.0;
-    if (p.huber > 0.0 && cc > p.huber * p.huber) {
-      const double r = sqrt(cc);
-      rho0 = 2.0 * p.huber * r - p.huber * p.huber;
-      rho1 = fmax(DBL_MIN, p.huber / r);
-    }
-    cost_obs = 0.5 * rho0;
-    if (!isfinite(cc)) atomicOr(&s_fail, 1);
-    if (JAC) {
-      p.rec[0 * p.rec_stride + obs] = rho1 * m11;
-      p.rec[1 * p.rec_stride + obs] = rho1 * m12;
-      p.rec[2 * p.rec_stride + obs] = rho1 * m22;
-      p.rec[3 * p.rec_stride + obs] = rho1 * b1;
-      p.rec[4 * p.rec_stride + obs] = rho1 * b2;
-      p.rec[5 * p.rec_stride + obs] = cost_obs;
-    }
-  }
-  if (FUSED) {
-    lds_barrier();        // every wave is done with the texel region / s_base before the finalisation reuses them
-    fused_wave_step_sums(bs_mcc, bs_st2, bs_x2);
-    fused_block_partials<WAVES>(p, bid, lane, wave, cost_obs, bs_mcc, bs_st2, bs_x2, s_red, s_fail, (int)threadIdx.x);
-    fused_finalize<WAVES>(p, lane, wave, &s_base[0][0], reinterpret_cast<double*>(s_raw), 0ull, (int)threadIdx.x);
-  } else {
-    const double ws = wave_sum(cost_obs);
-    if (lane == 0) s_red[wave] = ws;
-    lds_barrier();
-    if (threadIdx.x == 0) {
-      double a = 0.0;
-#pragma unroll
-      for (int w = 0; w < WAVES; ++w) a += s_red[w];
-      p.block_cost[blockIdx.x] = a;
-      p.block_fail[blockIdx.x] = s_fail;
-    }
-  }
+  if (!sample_prologue<FUSED>(p, false, (int)blockIdx.x, (int)threadIdx.x)) return;
+  sample_mc_wg<R, JAC, WAVES, FUSED, UNITW, MF>(p, frames_mc, n_channels, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x);
 }
 
 // =====================================================================================================
@@ -3121,18 +2908,26 @@ __device__ __forceinline__ void schur_body(SchurParams& p, char* smem, const int
 #undef PBA_TEP
 }
 
-__global__ __launch_bounds__(kTile, 2) void k_schur(SchurParams p_in) {
-  SchurParams p = p_in;
-  if (!PBA_PHASE_TIMING) p.dbg = nullptr;
-  if (p.pub_host_seq && blockIdx.x == 0)
-    lm_publish(p.lm, p.pub_state, p.pub_scal, p.pub_host_scal, p.pub_host_seq, p.pub_seq, threadIdx.x, kTile);
+// What k_schur and its batched form (pba_batch.h) do first, for workgroup `bid` of its window: workgroup 0 publishes the step the
+// previous enqueue decided; with the LM state on the device, a pass behind the end of the solve (or a final pass that is not needed)
+// leaves (returns false), the others take the current / candidate parity and the trust-region radius from the state.
+__device__ __forceinline__ bool schur_prologue(SchurParams& p, const bool keep_dbg, const int bid, const int tix) {
+  if (!keep_dbg) p.dbg = nullptr;
+  if (p.pub_host_seq && bid == 0)
+    lm_publish(p.lm, p.pub_state, p.pub_scal, p.pub_host_scal, p.pub_host_seq, p.pub_seq, tix, kTile);
   if (p.lm) {
-    if (p.lm->done && !p.final_pass) return;
-    if (p.final_pass && !lm_final_pass_needed(p.lm)) return;
+    if (p.lm->done && !p.final_pass) return false;
+    if (p.final_pass && !lm_final_pass_needed(p.lm)) return false;
     if (p.lm->cur != p.enq_cur) { p.xyz = p.xyz_alt; p.geom = p.geom_alt; p.rec = p.rec_alt; }
     p.radius = p.lm->radius;
     p.inv_radius = 1.0 / p.radius;
   }
+  return true;
+}
+
+__global__ __launch_bounds__(kTile, 2) void k_schur(SchurParams p_in) {
+  SchurParams p = p_in;
+  if (!schur_prologue(p, PBA_PHASE_TIMING != 0, (int)blockIdx.x, (int)threadIdx.x)) return;
   __shared__ __attribute__((aligned(16))) char smem[kSchurSmemBytes];
   schur_body<const void>(p, smem, (int)threadIdx.x, (int)blockIdx.x, (int)gridDim.x, nullptr, nullptr, true);
 }

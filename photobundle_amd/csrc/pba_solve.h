@@ -929,9 +929,10 @@ __device__ inline void flush_to_host(const LmState* lm, LmState* host_state, con
   lm_publish(lm, host_state, scal, host_scal, host_seq, seq, tid, nthreads);
 }
 
-// k_reduce_solve's body for workgroup `bid` of `grid` (thread `tid`): what the batched launch (pba_batch.h) runs per window.  The solo
-// kernel below keeps its own copy of these lines, so that its code generation stays as measured.
-__device__ __forceinline__ void reduce_solve_wg(const ReduceSolveParams& rsp, char* dyn_smem, const int bid, const int grid, const int tid) {
+// k_reduce_solve's body for workgroup `bid` of `grid` (thread `tid`): the solo kernel below runs it with the launch's own block and
+// grid, the batched launch (pba_batch.h) with the window's.  The parameters come by value: by reference the solo kernel keeps a copy
+// of them in scratch.
+__device__ __forceinline__ void reduce_solve_wg(const ReduceSolveParams rsp, char* dyn_smem, const int bid, const int grid, const int tid) {
   const LmState* lm = rsp.so.lm;
   ReduceParams rp = rsp.rp;
   const bool fin_mode = rsp.fin.host_seq != nullptr;
@@ -997,73 +998,9 @@ __device__ __forceinline__ void reduce_solve_wg(const ReduceSolveParams& rsp, ch
            grid, 0.01 * (double)(t_k1 - t_k0), 0.01 * (double)(__builtin_amdgcn_s_memrealtime() - t_k1));
 }
 
-// (reduce_solve_wg above is the batched launch's copy of this body: an edit here belongs there too)
 __global__ __launch_bounds__(kReduceThreads) void k_reduce_solve(ReduceSolveParams rsp) {
-  const LmState* lm = rsp.so.lm;
-  ReduceParams rp = rsp.rp;
-  const bool fin_mode = rsp.fin.host_seq != nullptr;
-  if (lm) {
-    if (lm->done && !rsp.so.final_pass) return;
-    if (rsp.so.final_pass && !lm_final_pass_needed(lm)) {
-      if (fin_mode && blockIdx.x == 0)
-        flush_to_host(lm, rsp.fin.host_state, rsp.so.scal, rsp.fin.host_scal, rsp.fin.log, rsp.fin.host_log, rsp.fin.max_log, rsp.fin.host_seq,
-                      rsp.fin.seq, threadIdx.x, kReduceThreads);
-      return;
-    }
-    if (lm->cur != rsp.so.enq_cur) { rp.block_cost = rsp.block_cost_alt; rp.block_fail = rsp.block_fail_alt; }
-  }
   extern __shared__ __attribute__((aligned(16))) char dyn_smem[];      // the solve's matrix (last workgroup only)
-  const unsigned long long t_k0 = PBA_PHASE_TIMING ? __builtin_amdgcn_s_memrealtime() : 0ull;
-  __shared__ double s_red[kReduceThreads / kReduceEntries][kReduceEntries + 1];
-  __shared__ int s_f[16];
-  __shared__ int s_last;
-  const int tid = threadIdx.x;
-  reduce_partials<1>(rp, s_red, s_f, (int)blockIdx.x, (int)gridDim.x);
-  // ---- ticket: the last workgroup to arrive solves ----------------------------------------------------------------
-  // every storing thread waits until its write-through stores have left the CU, then the workgroup takes its ticket
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned t = __hip_atomic_fetch_add(rsp.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = (t == gridDim.x - 1) ? 1 : 0;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  const bool wide = rsp.so.n_free > kSolveNarrowFree;
-  static_assert(kSolveWideThreads == kReduceThreads, "the wide solve uses the whole workgroup");
-  if (!wide && tid >= kSolveBlockedThreads) return;   // four of the eight waves leave; barriers below count the remaining four
-  if (tid == 0) *rsp.ticket = 0;
-  const unsigned long long t_k1 = PBA_PHASE_TIMING ? __builtin_amdgcn_s_memrealtime() : 0ull;
-  SolveParams so = rsp.so;
-  if (so.lm) {
-    if (so.lm->cur != so.enq_cur) {
-      so.cams = so.cams_alt; so.cams_cand = so.cams_cand_alt; so.geom = so.geom_alt;
-      if (so.geom_cand) so.geom_cand = so.geom_cand_alt;
-    }
-    so.radius = so.lm->radius;
-  }
-  so.packed = rp.packed;
-  if (wide) solve_blocked<true, kSolveWideThreads>(so, reinterpret_cast<double*>(dyn_smem), tid);
-  else solve_blocked<true, kSolveBlockedThreads>(so, reinterpret_cast<double*>(dyn_smem), tid);
-  if (fin_mode) {
-    // gradient-only decision + flush by this (last) workgroup: what k_decide and k_flush did as two more launches
-    const int nth = wide ? kSolveWideThreads : kSolveBlockedThreads;
-    __syncthreads();                                  // the epilogue's scalars have left (the barrier drains the stores)
-    if (tid == 0) {
-      double sl[kNumScal];
-      for (int k = 0; k < kNumScal; ++k) sl[k] = load_agent(so.scal + k);     // (max |g_p| came from another workgroup of this launch)
-      lm_decide(rsp.fin.lm, sl, rsp.fin.log, rsp.fin.max_log, 1);
-      if (rsp.fin.lm->done && rsp.fin.lm->done_seq == 0) rsp.fin.lm->done_seq = rsp.fin.seq;
-    }
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // thread 0's state / log stores (write-through) are read by the whole workgroup
-    flush_to_host(rsp.fin.lm, rsp.fin.host_state, so.scal, rsp.fin.host_scal, rsp.fin.log, rsp.fin.host_log, rsp.fin.max_log, rsp.fin.host_seq,
-                  rsp.fin.seq, tid, nth);
-  }
-  if (rsp.stamp && tid == 0) rsp.stamp[kStampEndSolve] = __builtin_amdgcn_s_memrealtime();
-  if (PBA_PHASE_TIMING && rsp.so.dbg && tid == 0)
-    printf("k_reduce_solve: last workgroup %d of %d reached the solve %.2f us after its own start, finished it %.2f us later\n", (int)blockIdx.x,
-           (int)gridDim.x, 0.01 * (double)(t_k1 - t_k0), 0.01 * (double)(__builtin_amdgcn_s_memrealtime() - t_k1));
+  reduce_solve_wg(rsp, dyn_smem, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x);
 }
 
 }  // namespace pba
