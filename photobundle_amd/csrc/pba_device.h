@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/pba.h"
+#include "pba_lm_rules.h"      // the scalar block of a step (Scal), LmState and the trust-region rules
 
 namespace pba {
 
@@ -36,57 +37,6 @@ struct CamGeom {
   int32_t is_free;    // 0 for the constant camera
   int32_t free_index; // index among free cameras, -1 if constant
   int32_t pad;
-};
-
-// Device scalar block (Engine::d_scal), grouped so that the multi-rank transports can reduce slices in place.
-enum Scal {
-  // --- group B, SUM over ranks after the cost pass -------------------------------------------------
-  kCandCost = 0,    // candidate cost (local shard)
-  kMccPts,          // point part of the model cost change
-  kStep2Pts,        // sum delta_p^2
-  kX2Pts,           // sum xyz^2 at the current point
-  kSumBCount = 4,
-  // --- group M, MAX over ranks ----------------------------------------------------------------------
-  kGmaxPts = 8,     // max |g_p|
-  kSchurFail,       // > 0: a damped point block was not PD
-  kEvalFailLin,     // > 0: non-finite residual block in the Jacobian pass
-  kEvalFailCand,    // > 0: non-finite residual block in the cost pass
-  kMaxCount = 4,
-  // --- replicated (identical on every rank, never reduced) --------------------------------------------
-  kMccCams = 16,
-  kStep2Cams,
-  kX2Cams,
-  kGmaxCams,
-  kGnorm2Cams,
-  kSolveOk,         // reduced-system Cholesky succeeded and the camera step is finite
-  kCostLin,         // GLOBAL cost at the linearisation point (copied out of the reduced packed buffer)
-  kGnorm2Pts,       // GLOBAL sum g_p^2
-  kNumScal = 32
-};
-
-// ---- device-resident Levenberg-Marquardt state (asynchronous driver) -------------------------------------------
-// The trust-region decisions of pba_lm.cpp (Ceres TrustRegionMinimizer / LevenbergMarquardtStrategy) evaluated by
-// the LAST workgroup of the candidate pass, so that the host can enqueue iterations back to back without a round
-// trip per step.  The host still owns the loop: it enqueues, watches `done`, and reads the iteration log.
-enum LmTermination { kLmRunning = 0, kLmMaxIterations, kLmGradientTolerance, kLmMinRadius, kLmParameterTolerance,
-                     kLmFunctionTolerance, kLmInvalidSteps, kLmEvalFailure };
-
-struct LmState {
-  double radius, decrease_factor, x_cost, minimum_cost, initial_cost;
-  double last_value[2];        // termination detail (e.g. step norm ratio)
-  int32_t cur;                 // parity of the current point
-  int32_t iteration;           // iterations completed (log entries written = n_log)
-  int32_t done;                // LmTermination
-  int32_t num_invalid, num_successful, num_unsuccessful;
-  int32_t pending_grad;        // log index still waiting for the gradient norms of its (accepted) point, -1 none
-  int32_t n_log;
-  int32_t first;               // 1 until iteration 0 has been logged
-  int32_t pad;
-  // options
-  double function_tolerance, gradient_tolerance, parameter_tolerance;
-  double max_radius, min_radius, min_relative_decrease;
-  int32_t max_num_iterations, max_invalid;
-  unsigned long long done_seq;   // sequence number of the step that terminated the solve (0 while running)
 };
 
 }  // namespace pba

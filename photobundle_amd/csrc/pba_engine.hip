@@ -1558,34 +1558,50 @@ int pba_linearize(pba_engine* e, double* cost) {
   return PBA_OK;
 }
 
-// Waits for the device to publish the scalar block of step `seq` and unpacks it (the end of every pba_step).
-static int wait_step_scalars(pba_engine* e, unsigned long long seq, bool multi, pba_step_info* out) {
-  // wait for the device to publish this step's scalar block (host-mapped memory, no driver round trip)
-  {
-    volatile unsigned long long* h_seq = reinterpret_cast<volatile unsigned long long*>(e->h_scal + kNumScal);
-    unsigned long spins = 0;
-    double t_first = -1.0;
+// Spins on the host-mapped sequence number until step `seq` is published.  exact: a synchronous step -- the number must become `seq`
+// itself; else a pipelined wait -- any number from `seq` on will do, and a terminated solve (whose remaining kernels are no-ops) may
+// drain the stream without ever publishing it.
+static int wait_published(pba_engine* e, unsigned long long seq, bool exact) {
+  volatile unsigned long long* h_seq = reinterpret_cast<volatile unsigned long long*>(e->h_scal + kNumScal);
+  const auto pending = [&] { return exact ? *h_seq != seq : *h_seq < seq; };
+  unsigned long spins = 0;
+  double t_first = -1.0;
+  { const int rcc = comm_failed(e); if (rcc) return rcc; }
+  while (pending()) {
     { const int rcc = comm_failed(e); if (rcc) return rcc; }
-    while (*h_seq != seq) {
-      { const int rcc = comm_failed(e); if (rcc) return rcc; }
-      // hipStreamQuery is not free for the device (it showed up as a ~6 us bubble in front of the next kernel), so it only
-      // serves as a watchdog here: roughly every 50 ms of spinning
-      if ((++spins & 0x3ffffff) == 0) {
-        const hipError_t q = hipStreamQuery(e->stream);
-        if (q != hipSuccess && q != hipErrorNotReady) return fail(e, PBA_ERR_HIP, "stream error while waiting: %s", hipGetErrorString(q));
-        if (q == hipSuccess && *h_seq != seq) return fail(e, PBA_ERR_HIP, "step finished without publishing its scalars");
-        const double t = wall_seconds();
-        if (t_first < 0.0) t_first = t;
-        else if (t - t_first > e->wait_timeout_s) {
-          e->poisoned = true;
-          return fail(e, multi ? PBA_ERR_COMM : PBA_ERR_HIP, "timed out after %.0f s waiting for step %llu", e->wait_timeout_s, seq);
-        }
+    // hipStreamQuery is not free for the device (it showed up as a ~6 us bubble in front of the next kernel), so it only
+    // serves as a watchdog here: roughly every 50 ms of spinning
+    if ((++spins & 0x3ffffff) == 0) {
+      const hipError_t q = hipStreamQuery(e->stream);
+      if (q != hipSuccess && q != hipErrorNotReady) return fail(e, PBA_ERR_HIP, "stream error while waiting: %s", hipGetErrorString(q));
+      if (q == hipSuccess && pending()) {
+        if (exact) return fail(e, PBA_ERR_HIP, "step finished without publishing its scalars");
+        if (reinterpret_cast<volatile LmState*>(e->h_lm)->done) return PBA_OK;
+        return fail(e, PBA_ERR_HIP, "step finished without publishing");
+      }
+      // a collective that never completes (a peer died, or the ranks disagree on the number of enqueued steps) would
+      // otherwise spin forever: bounded by PBA_WAIT_TIMEOUT_S (default 120 s) of wall-clock per awaited step
+      const double t = wall_seconds();
+      if (t_first < 0.0) t_first = t;
+      else if (t - t_first > e->wait_timeout_s) {
+        e->poisoned = true;
+        const int code = e->comm.multi() ? PBA_ERR_COMM : PBA_ERR_HIP;
+        if (exact) return fail(e, code, "timed out after %.0f s waiting for step %llu", e->wait_timeout_s, seq);
+        return fail(e, code, "timed out after %.0f s waiting for step %llu (last published %llu)", e->wait_timeout_s, seq,
+                    (unsigned long long)*h_seq);
       }
     }
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    // the sequence number may already have been there when the wait was entered: the error word is checked on the way out too
-    { const int rcc = comm_failed(e); if (rcc) return rcc; }
   }
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  // the sequence number may already have been there when the wait was entered (normal with the pipelined driver): the error word is
+  // checked on the way out too
+  return comm_failed(e);
+}
+
+// Waits for the device to publish the scalar block of step `seq` and unpacks it (the end of every pba_step); scal != nullptr also
+// gets the raw block (kNumScal doubles, what lm_decide reads).  PBA_ERR_NUMERIC comes with both outputs filled.
+static int wait_step_scalars(pba_engine* e, unsigned long long seq, pba_step_info* out, double* scal) {
+  { const int rcw = wait_published(e, seq, true); if (rcw) return rcw; }
   if (e->profile) { HIP_TRY(e, hipStreamSynchronize(e->stream)); ev_collect(e); }
   double s[kNumScal];
   for (int k = 0; k < kNumScal; ++k) s[k] = reinterpret_cast<volatile double*>(e->h_scal)[k];
@@ -1598,13 +1614,28 @@ static int wait_step_scalars(pba_engine* e, unsigned long long seq, bool multi, 
   out->candidate_cost = s[kCandCost];
   out->linear_solver_ok = (s[kSolveOk] > 0.5 && s[kSchurFail] < 0.5) ? 1 : 0;
   out->eval_ok = (s[kEvalFailCand] < 0.5 && std::isfinite(s[kCandCost])) ? 1 : 0;
+  if (scal) std::memcpy(scal, s, sizeof(s));
   if (s[kEvalFailLin] > 0.5) return fail(e, PBA_ERR_NUMERIC, "non-finite residual block at the linearisation point");
   return PBA_OK;
 }
 
+// The candidate pass of a host-stepped step: a Jacobian pass when speculating on acceptance (the candidate is then already linearised
+// when pba_accept makes it the current point), else a cost pass.  fused: the kernel that also back-substitutes and finalises the step.
+static void candidate_pass(pba_engine* e, const SampleParams& sp, int cand, bool fused) {
+  const int k = e->speculate ? 0 : 1;
+  ev_begin(e, k);
+  if (fused) { if (e->speculate) launch_sample<true, true>(e, sp); else launch_sample<false, true>(e, sp); }
+  else { if (e->speculate) launch_sample<true>(e, sp); else launch_sample<false>(e, sp); }
+  ev_end(e, k);
+  ++(e->speculate ? e->jac_passes : e->cost_passes);
+  e->cost_blocks[cand] = fused ? e->fused_grid : e->sample_grid;
+  e->lin_valid[cand] = e->speculate;
+}
+
 // pba_step of the pose-only mode (pba_pose.h): per-camera sums of the stored linearisation (once per linearisation), the block-diagonal
 // damped solve, the candidate pass at the candidate cameras with the unchanged points, the candidate cost.
-static int pose_step(pba_engine* e, double radius, int32_t init_scale, const pba_solver_options* o, pba_step_info* out, int grad_only) {
+static int pose_step(pba_engine* e, double radius, int32_t init_scale, const pba_solver_options* o, pba_step_info* out, double* scal,
+                     int grad_only) {
   const int cur = e->cur, cand = 1 - e->cur;
   int rc;
   if ((rc = pose_sync_points(e))) return rc;
@@ -1640,41 +1671,30 @@ static int pose_step(pba_engine* e, double radius, int32_t init_scale, const pba
   if (!grad_only) {
     // candidate point: Jacobian pass when speculating on acceptance, else cost pass; the points are the current ones
     SampleParams sp = make_sample_params(e, cand);
-    if (e->speculate) {
-      ev_begin(e, 0);
-      launch_sample<true>(e, sp);
-      ev_end(e, 0);
-      e->jac_passes++;
-    } else {
-      ev_begin(e, 1);
-      launch_sample<false>(e, sp);
-      ev_end(e, 1);
-      e->cost_passes++;
-    }
-    e->cost_blocks[cand] = e->sample_grid;
-    e->lin_valid[cand] = e->speculate;
+    candidate_pass(e, sp, cand, false);
     hipLaunchKernelGGL(k_pose_finalize, dim3(1), dim3(kPoseThreads), 0, e->stream, (const double*)e->d_block_cost[cand],
                        (const int32_t*)e->d_block_fail[cand], e->sample_grid, e->d_scal, e->h_scal_dev, h_seq_dev, seq);
   } else {
     hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, e->stream, e->d_scal, e->h_scal_dev, h_seq_dev, seq, (const double*)nullptr, 1);
   }
   HIP_TRY(e, hipGetLastError());
-  return wait_step_scalars(e, seq, false, out);
+  return wait_step_scalars(e, seq, out, scal);
 }
 
 int pba_step(pba_engine* e, double radius, int32_t init_scale, const pba_solver_options* o, pba_step_info* out) {
-  return pba_internal_step(e, radius, init_scale, o, out, 0);
+  return pba_internal_step(e, radius, init_scale, o, out, nullptr, 0);
 }
 
-// grad_only != 0: stop after the reduced solve (cost / gradient norms of the linearisation point only).
-int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pba_solver_options* o, pba_step_info* out,
+// grad_only != 0: stop after the reduced solve (cost / gradient norms of the linearisation point only).  scal: nullptr, or kNumScal
+// doubles for the step's raw scalar block.
+int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pba_solver_options* o, pba_step_info* out, double* scal,
                       int grad_only) {
   if (!e || !o || !out || !(radius > 0.0)) return PBA_ERR_INVALID;
   e->last_driver = 3;
   if (!e->have_lin) return fail(e, PBA_ERR_STATE, "call order violated: pba_step before pba_linearize");
   PBA_NOT_POISONED(e);
   HIP_TRY(e, hipSetDevice(e->cfg.device));
-  if (e->points_const) return pose_step(e, radius, init_scale, o, out, grad_only);
+  if (e->points_const) return pose_step(e, radius, init_scale, o, out, scal, grad_only);
   const int cur = e->cur, cand = 1 - e->cur;
   const int n = 6 * e->n_free;
   const bool multi = e->comm.multi();
@@ -1720,19 +1740,7 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
       if (rcx) return rcx;
       xchg_packed = true;
     }
-    if (e->speculate) {
-      ev_begin(e, 0);
-      launch_sample<true, true>(e, sp);
-      ev_end(e, 0);
-      e->jac_passes++;
-    } else {
-      ev_begin(e, 1);
-      launch_sample<false, true>(e, sp);
-      ev_end(e, 1);
-      e->cost_passes++;
-    }
-    e->cost_blocks[cand] = e->fused_grid;
-    e->lin_valid[cand] = e->speculate;
+    candidate_pass(e, sp, cand, true);
     if (sp.dbg) dump_fused_sample_timeline(e, sp.dbg);
   } else if (!grad_only) {
     BacksubParams bs{};
@@ -1744,19 +1752,7 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
     hipLaunchKernelGGL(k_backsub, dim3(e->backsub_grid), dim3(256), 0, e->stream, bs);
     // candidate point: Jacobian pass when speculating on acceptance, else cost pass
     SampleParams sp = make_sample_params(e, cand);
-    if (e->speculate) {
-      ev_begin(e, 0);
-      launch_sample<true>(e, sp);
-      ev_end(e, 0);
-      e->jac_passes++;
-    } else {
-      ev_begin(e, 1);
-      launch_sample<false>(e, sp);
-      ev_end(e, 1);
-      e->cost_passes++;
-    }
-    e->cost_blocks[cand] = e->sample_grid;
-    e->lin_valid[cand] = e->speculate;
+    candidate_pass(e, sp, cand, false);
     hipLaunchKernelGGL(k_finalize_step, dim3(1), dim3(256), 0, e->stream, e->d_bs_out, e->backsub_grid, e->d_block_cost[cand],
                        e->d_block_fail[cand], e->sample_grid, e->d_scal, multi ? nullptr : e->h_scal_dev, h_seq_dev, seq);
   }
@@ -1770,7 +1766,7 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
                        (const double*)(multi ? e->d_xchg : nullptr), e->comm.world);
     HIP_TRY(e, hipGetLastError());
   }
-  return wait_step_scalars(e, seq, multi, out);
+  return wait_step_scalars(e, seq, out, scal);
 }
 
 int pba_accept(pba_engine* e) {
@@ -1993,14 +1989,7 @@ int pba_internal_async_begin(pba_engine* e, const pba_solver_options* o) {
   { const int rc0 = check_ready(e, "pba_solve"); if (rc0) return rc0; }
   PBA_NOT_POISONED(e);
   HIP_TRY(e, hipSetDevice(e->cfg.device));
-  LmState st;
-  std::memset(&st, 0, sizeof(st));
-  st.radius = o->initial_trust_region_radius; st.decrease_factor = 2.0;
-  st.cur = e->cur; st.pending_grad = -1; st.first = 1;
-  st.function_tolerance = o->function_tolerance; st.gradient_tolerance = o->gradient_tolerance;
-  st.parameter_tolerance = o->parameter_tolerance; st.max_radius = o->max_trust_region_radius;
-  st.min_radius = o->min_trust_region_radius; st.min_relative_decrease = o->min_relative_decrease;
-  st.max_num_iterations = o->max_num_iterations; st.max_invalid = o->max_num_consecutive_invalid_steps;
+  const LmState st = lm_initial_state(o, e->cur);
   *e->h_lm = st;
   // The device copy of the initial state is made by the first kernel of the solve (workgroup 0 of the kind-0 sampling pass reads the
   // host-mapped mirror: SampleParams::lm_init_*); PBA_LM_INIT_KERNEL=1 keeps the separate launch of rounds 3-4.
@@ -2152,37 +2141,7 @@ int pba_internal_async_enqueue(pba_engine* e, int kind, int init_scale, const pb
   return PBA_OK;
 }
 
-int pba_internal_async_wait(pba_engine* e, unsigned long long seq) {
-  volatile unsigned long long* h_seq = reinterpret_cast<volatile unsigned long long*>(e->h_scal + kNumScal);
-  unsigned long spins = 0;
-  double t_first = -1.0;
-  { const int rcc = comm_failed(e); if (rcc) return rcc; }
-  while (*h_seq < seq) {
-    { const int rcc = comm_failed(e); if (rcc) return rcc; }
-    // hipStreamQuery is not free for the device (it showed up as a ~6 us bubble in front of the next kernel), so it only
-    // serves as a watchdog here: roughly every 50 ms of spinning
-    if ((++spins & 0x3ffffff) == 0) {
-      const hipError_t q = hipStreamQuery(e->stream);
-      if (q != hipSuccess && q != hipErrorNotReady) return fail(e, PBA_ERR_HIP, "stream error while waiting: %s", hipGetErrorString(q));
-      if (q == hipSuccess && *h_seq < seq) {
-        // a terminated solve turns the remaining kernels into no-ops that publish nothing
-        if (reinterpret_cast<volatile LmState*>(e->h_lm)->done) return PBA_OK;
-        return fail(e, PBA_ERR_HIP, "step finished without publishing");
-      }
-      // a collective that never completes (a peer died, or the ranks disagree on the number of enqueued steps) would
-      // otherwise spin forever: bounded by PBA_WAIT_TIMEOUT_S (default 120 s) of wall-clock per awaited step
-      const double t = wall_seconds();
-      if (t_first < 0.0) t_first = t;
-      else if (t - t_first > e->wait_timeout_s) {
-        e->poisoned = true;
-        return fail(e, e->comm.multi() ? PBA_ERR_COMM : PBA_ERR_HIP, "timed out after %.0f s waiting for step %llu (last published %llu)",
-                    e->wait_timeout_s, seq, (unsigned long long)*h_seq);
-      }
-    }
-  }
-  __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  return comm_failed(e);      // (normal with the pipelined driver: the awaited number was already visible on entry)
-}
+int pba_internal_async_wait(pba_engine* e, unsigned long long seq) { return wait_published(e, seq, false); }
 
 // ---- resident solve ------------------------------------------------------------------------------------------------
 
@@ -2265,15 +2224,7 @@ int pba_internal_resident_launch(pba_engine* e, const pba_solver_options* o, uns
   { const int rc0 = check_ready(e, "pba_solve"); if (rc0) return rc0; }
   PBA_NOT_POISONED(e);
   HIP_TRY(e, hipSetDevice(e->cfg.device));
-  LmState st;
-  std::memset(&st, 0, sizeof(st));
-  st.radius = o->initial_trust_region_radius; st.decrease_factor = 2.0;
-  st.cur = e->cur; st.pending_grad = -1; st.first = 1;
-  st.function_tolerance = o->function_tolerance; st.gradient_tolerance = o->gradient_tolerance;
-  st.parameter_tolerance = o->parameter_tolerance; st.max_radius = o->max_trust_region_radius;
-  st.min_radius = o->min_trust_region_radius; st.min_relative_decrease = o->min_relative_decrease;
-  st.max_num_iterations = o->max_num_iterations; st.max_invalid = o->max_num_consecutive_invalid_steps;
-  *e->h_lm = st;
+  *e->h_lm = lm_initial_state(o, e->cur);
   __atomic_thread_fence(__ATOMIC_RELEASE);
   ResidentParams P{};
   P.frames = e->d_frames; P.desc = e->d_desc; P.w2 = e->d_w2; P.tile_info = e->d_tile_info; P.lane_rec = e->d_lane_rec;

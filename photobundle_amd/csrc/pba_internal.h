@@ -3,8 +3,9 @@
 #include "../../include/pba.h"
 
 extern "C" {
-// grad_only != 0: stop after the reduced solve (cost / gradient norms of the linearisation point only).
-int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pba_solver_options* o, pba_step_info* out,
+// grad_only != 0: stop after the reduced solve (cost / gradient norms of the linearisation point only).  scal: nullptr, or 32 doubles
+// for the step's raw scalar block (pba_lm_rules.h: Scal), which PBA_ERR_NUMERIC fills too.
+int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pba_solver_options* o, pba_step_info* out, double* scal,
                       int grad_only);
 int pba_internal_ready(pba_engine* e);   /* PBA_OK, or PBA_ERR_STATE with the reason in pba_last_error */
 int pba_internal_world(const pba_engine* e);

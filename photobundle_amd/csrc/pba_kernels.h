@@ -375,136 +375,7 @@ __device__ __forceinline__ void point_jacobian(const double* __restrict__ rays, 
   }
 }
 
-// =====================================================================================================
-// device-side trust-region bookkeeping (asynchronous driver): the decisions of pba_lm.cpp for ONE step
-// =====================================================================================================
-__device__ __forceinline__ void lm_step_rejected(LmState* st) {   // LevenbergMarquardtStrategy::StepRejected
-  st->radius = st->radius / st->decrease_factor;
-  st->decrease_factor *= 2.0;
-}
-
-__device__ inline void lm_log(LmState* st, pba_iteration_summary* log, int max_log, const pba_iteration_summary& it) {
-  if (st->n_log < max_log) log[st->n_log] = it;
-  st->n_log++;
-}
-
-// `s` = the step's (fully reduced) scalar block.  grad_only: only the gradient norms of the current point are valid.
-// Gate of the final (gradient-only) pass, evaluated on the device so that the host can enqueue that pass without first
-// reading the state back: it is needed for iteration zero of a zero-iteration solve and when the iteration limit was
-// reached right after an accepted step (whose gradient norms are still to be reported).
-__device__ __forceinline__ bool lm_final_pass_needed(const LmState* st) {
-  return st->first || (st->pending_grad >= 0 && (st->done == kLmRunning || st->done == kLmMaxIterations));
-}
-
-__device__ inline void lm_decide(LmState* st, const double* s, pba_iteration_summary* log, int max_log, int grad_only) {
-  const double gmax = fmax(s[kGmaxPts], s[kGmaxCams]);
-  const double gnorm = sqrt(s[kGnorm2Pts] + s[kGnorm2Cams]);
-  if (st->done) {
-    // final pass after the iteration limit: only report the gradient norms of the last accepted point
-    if (grad_only && st->done == kLmMaxIterations && st->pending_grad >= 0 && !st->first) {
-      if (st->pending_grad < max_log) { log[st->pending_grad].gradient_max_norm = gmax; log[st->pending_grad].gradient_norm = gnorm; }
-      st->pending_grad = -1;
-    }
-    return;
-  }
-  pba_iteration_summary it;
-  memset(&it, 0, sizeof(it));
-  it.eta = 1e-1;
-  if (st->first) {
-    // IterationZero
-    if (s[kEvalFailLin] > 0.5) { st->done = kLmEvalFailure; return; }
-    st->first = 0;
-    st->x_cost = s[kCostLin];
-    st->initial_cost = st->x_cost;
-    st->minimum_cost = st->x_cost;
-    it.iteration = 0; it.cost = st->x_cost; it.gradient_max_norm = gmax; it.gradient_norm = gnorm;
-    it.step_is_valid = 1; it.step_is_successful = 1; it.trust_region_radius = st->radius;
-    st->num_successful = 1;
-    lm_log(st, log, max_log, it);
-    if (0 >= st->max_num_iterations) st->done = kLmMaxIterations;
-    else if (gmax <= st->gradient_tolerance) { st->done = kLmGradientTolerance; st->last_value[0] = gmax; }
-    else if (st->radius <= st->min_radius) st->done = kLmMinRadius;
-    if (st->done) return;
-    // the record of iteration zero is out; iteration one starts from a clean one (its step_is_successful / step_is_valid
-    // flags used to survive into a REJECTED first step's log entry)
-    memset(&it, 0, sizeof(it));
-    it.eta = 1e-1;
-  } else if (st->pending_grad >= 0) {
-    // gradient norms of the point accepted by the previous iteration + its deferred termination checks
-    if (st->pending_grad < max_log) { log[st->pending_grad].gradient_max_norm = gmax; log[st->pending_grad].gradient_norm = gnorm; }
-    st->pending_grad = -1;
-    if (s[kEvalFailLin] > 0.5) { st->done = kLmEvalFailure; return; }
-    if (gmax <= st->gradient_tolerance) { st->done = kLmGradientTolerance; st->last_value[0] = gmax; return; }
-    if (st->radius <= st->min_radius) { st->done = kLmMinRadius; return; }
-  }
-  if (grad_only) return;
-
-  const int iteration = st->iteration + 1;
-  it.iteration = iteration;
-  it.gradient_max_norm = gmax; it.gradient_norm = gnorm;
-  it.linear_solver_iterations = 1;
-  it.model_cost_change = s[kMccPts] + s[kMccCams];
-  const bool solver_ok = s[kSolveOk] > 0.5 && s[kSchurFail] < 0.5;
-  const bool step_is_valid = solver_ok && it.model_cost_change > 0.0;
-  bool successful = false;
-  if (!step_is_valid) {
-    // HandleInvalidStep
-    st->num_invalid++;
-    it.cost = st->x_cost;
-    if (st->num_invalid >= st->max_invalid) {
-      it.trust_region_radius = st->radius;
-      lm_log(st, log, max_log, it);
-      st->iteration = iteration;
-      st->done = kLmInvalidSteps;
-      return;
-    }
-    lm_step_rejected(st);
-  } else {
-    it.step_is_valid = 1;
-    st->num_invalid = 0;
-    const bool eval_ok = s[kEvalFailCand] < 0.5 && isfinite(s[kCandCost]);
-    const double candidate_cost = eval_ok ? s[kCandCost] : DBL_MAX;
-    it.candidate_cost = candidate_cost;
-    it.step_norm = sqrt(s[kStep2Pts] + s[kStep2Cams]);
-    const double x_norm = sqrt(s[kX2Pts] + s[kX2Cams]);
-    if (it.step_norm <= st->parameter_tolerance * (x_norm + st->parameter_tolerance)) {   // ParameterToleranceReached
-      st->done = kLmParameterTolerance;
-      st->last_value[0] = it.step_norm / (x_norm + st->parameter_tolerance);
-      return;
-    }
-    it.cost_change = st->x_cost - candidate_cost;
-    if (fabs(it.cost_change) <= st->function_tolerance * st->x_cost) {                    // FunctionToleranceReached
-      st->done = kLmFunctionTolerance;
-      st->last_value[0] = fabs(it.cost_change) / st->x_cost;
-      return;
-    }
-    it.relative_decrease = it.cost_change / it.model_cost_change;
-    if (it.relative_decrease > st->min_relative_decrease) {
-      // HandleSuccessfulStep + LevenbergMarquardtStrategy::StepAccepted
-      successful = true;
-      st->cur ^= 1;
-      st->x_cost = candidate_cost;
-      const double t = 2.0 * it.relative_decrease - 1.0;
-      st->radius = st->radius / fmax(1.0 / 3.0, 1.0 - t * t * t);
-      st->radius = fmin(st->max_radius, st->radius);
-      st->decrease_factor = 2.0;
-      it.step_is_successful = 1;
-      it.cost = st->x_cost;
-      st->pending_grad = st->n_log;
-    } else {
-      lm_step_rejected(st);
-      it.cost = candidate_cost;
-    }
-  }
-  // FinalizeIterationAndCheckIfMinimizerCanContinue (gradient tolerance deferred to the next decision)
-  if (successful) { st->num_successful++; st->minimum_cost = st->x_cost; }
-  else st->num_unsuccessful++;
-  it.trust_region_radius = st->radius;
-  lm_log(st, log, max_log, it);
-  st->iteration = iteration;
-  if (iteration >= st->max_num_iterations) st->done = kLmMaxIterations;
-  else if (!successful && st->radius <= st->min_radius) st->done = kLmMinRadius;
-}
+// (the trust-region decision of a step, lm_decide, is pba_lm_rules.h)
 
 // Publishes state + scalars to the host mirror, then the sequence number.
 // Host-mapped (fine-grained, uncached) destinations: the stores go straight to the host, so waiting for their

@@ -1,19 +1,25 @@
-// pba_lm.cpp -- host Levenberg-Marquardt driver: replaces ceres::Solve at reference src/photobundle.cc:829.
+// pba_lm.cpp -- the solve drivers: replaces ceres::Solve at reference src/photobundle.cc:829.
 //
-// Control flow = Ceres (>= 1.12) TrustRegionMinimizer + LevenbergMarquardtStrategy with the settings of
-// GetSolverOptions (photobundle.cc:738-761) and the Ceres defaults listed in SURVEY.md 8c.  All heavy work is
-// behind the C-ABI primitives (pba_linearize / pba_step / pba_accept); this file only decides.
+// ONE rule set, four schedulers.  The trust-region rules (Ceres TrustRegionMinimizer + LevenbergMarquardtStrategy) are pba_lm_rules.h:
+// an LmState and one lm_decide per step on the step's scalar block.  The drivers of this file only differ in WHERE that decision runs
+// and how the device work around it is scheduled; all heavy work is behind the engine (pba_engine.hip):
+//   host-stepped  solve_host_stepped   one step per round trip, lm_decide on the host.  Everything the others do not cover: wide windows,
+//                                      pose-only solves, PBA_FUSE=0 / PBA_ASYNC=0, the precision-sweep flags, profiling, iteration limits
+//                                      beyond the device log, the callback transport without peer exchange
+//   pipelined     solve_async          lm_decide in the last workgroup of every candidate pass; the host enqueues steps back to back
+//   batched       pba_solve_batch      the pipelined schedule for n independent windows in shared launches
+//   resident      solve_resident       the whole solve as one cooperative launch, lm_decide in its serial workgroup
+// All of them report through summarize_solve, which holds every termination message.
 //
-// One deviation in scheduling (not in results): the gradient norms of a freshly accepted point come out of the
-// same device pass that computes the NEXT trust-region step, so that step is computed speculatively right after
-// an acceptance; if the iteration then terminates the solve (gradient tolerance / iteration limit) the
-// speculative step is simply dropped (at the iteration limit only the gradient part is run).
+// One deviation from Ceres in scheduling (not in results), common to all drivers: the gradient norms of a freshly accepted point come
+// out of the same device pass that computes the NEXT trust-region step, so that step is computed speculatively right after an
+// acceptance; if the iteration then terminates the solve (gradient tolerance / iteration limit) the speculative step is simply
+// dropped (at the iteration limit only the gradient part is run).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <limits>
 #include <vector>
 
 #include "../../include/pba.h"
@@ -25,8 +31,11 @@ namespace {
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 }
 
-static int summarize_device_solve(pba_engine* e, const pba_solver_options* o, pba_solver_summary* sum, pba_iteration_summary* its,
-                                  int32_t max_out, double t_start, bool verbose, int64_t jac_passes);
+static int summarize_solve(pba_engine* e, const pba_solver_options* o, const pba::LmState* st, const pba_iteration_summary* device_log,
+                           pba_solver_summary* sum, pba_iteration_summary* its, int32_t max_out, double t_start, bool verbose,
+                           int64_t jac_passes);
+// the state a device driver left in the engine's host mirror
+static const pba::LmState* mirror(const pba_engine* e) { return static_cast<const pba::LmState*>(pba_internal_async_state(e)); }
 
 // Resident variant (pba_resident.h): the whole solve is ONE cooperative launch -- every workgroup keeps its tiles' state in registers
 // across the iterations, the serial workgroup takes the same decisions (lm_decide) -- and the host only waits for the flush.
@@ -41,15 +50,15 @@ static int solve_resident(pba_engine* e, const pba_solver_options* o, pba_solver
   if (rc) return rc;
   if ((rc = pba_internal_async_wait(e, seq))) { pba_internal_resident_failed(e); return rc; }
   if ((rc = pba_internal_async_end(e))) return rc;
-  const pba::LmState* st = static_cast<const pba::LmState*>(pba_internal_async_state(e));
+  const pba::LmState* st = mirror(e);
   pba_internal_resident_done(e, st->iteration);
   pba_internal_resident_trace(e, st->iteration);
   // one Jacobian pass at the initial point + one (speculative) Jacobian pass per step taken
-  return summarize_device_solve(e, o, sum, its, max_out, t_start, verbose, 1 + (int64_t)st->iteration);
+  return summarize_solve(e, o, st, pba_internal_async_log(e), sum, its, max_out, t_start, verbose, 1 + (int64_t)st->iteration);
 }
 
 // Asynchronous variant: the same trust-region rules are evaluated on the device by the last workgroup of every
-// candidate pass (pba_kernels.h: lm_decide), so the host enqueues iterations back to back (at most kAhead in flight
+// candidate pass (lm_decide), so the host enqueues iterations back to back (at most kAhead in flight
 // beyond the last one it has seen finish) instead of paying a launch + completion round trip per step.
 static int solve_async(pba_engine* e, const pba_solver_options* o, pba_solver_summary* sum, pba_iteration_summary* its,
                        int32_t max_out, double t_start, bool verbose) {
@@ -101,30 +110,34 @@ static int solve_async(pba_engine* e, const pba_solver_options* o, pba_solver_su
   tt[6] = now();
   if (tr) std::fprintf(stderr, "solve_async us: entry->begin %.1f, begin %.1f, enqueue0 %.1f, loop %.1f, final enqueues %.1f, final wait %.1f, end %.1f\n",
                        1e6 * (tt[0] - t_start), 1e6 * (tt[1] - tt[0]), 1e6 * (tt[2] - tt[1]), 1e6 * (tt[3] - tt[2]), 1e6 * (tt[4] - tt[3]), 1e6 * (tt[5] - tt[4]), 1e6 * (tt[6] - tt[5]));
-  return summarize_device_solve(e, o, sum, its, max_out, t_start, verbose, -1);
+  return summarize_solve(e, o, mirror(e), pba_internal_async_log(e), sum, its, max_out, t_start, verbose, -1);
 }
 
-// The host mirror of the device-side trust-region state and iteration log -> pba_solver_summary / iteration summaries.
-// jac_passes < 0: the pass counters of the engine (asynchronous driver); else the count to report (resident solve).
-static int summarize_device_solve(pba_engine* e, const pba_solver_options* o, pba_solver_summary* sum, pba_iteration_summary* its,
-                                  int32_t max_out, double t_start, bool verbose, int64_t jac_passes) {
-  using pba::LmState;
-  LmState fin;
-  std::memcpy(&fin, const_cast<const LmState*>(static_cast<const LmState*>(pba_internal_async_state(e))), sizeof(fin));
-  const pba_iteration_summary* log = pba_internal_async_log(e);
+// The final trust-region state and the iteration log -> pba_solver_summary: every driver ends here, and no termination message is
+// written anywhere else.  device_log: the engine's host mirror of a device driver's log, copied to `its` with the solve's time spread
+// evenly over the entries; nullptr: the driver logged into `its` itself.
+// jac_passes < 0: the pass counters of the engine; else the count to report (resident solve).
+static int summarize_solve(pba_engine* e, const pba_solver_options* o, const pba::LmState* st, const pba_iteration_summary* device_log,
+                           pba_solver_summary* sum, pba_iteration_summary* its, int32_t max_out, double t_start, bool verbose,
+                           int64_t jac_passes) {
+  const pba::LmState fin = *st;
   const double total = now() - t_start;
   const int n_log = fin.n_log;
   for (int i = 0; i < n_log && i < max_out && its; ++i) {
-    its[i] = log[i];
-    its[i].iteration_time_in_seconds = total / (n_log > 0 ? n_log : 1);
-    its[i].cumulative_time_in_seconds = total * (i + 1) / (n_log > 0 ? n_log : 1);
+    if (device_log) {
+      its[i] = device_log[i];
+      its[i].iteration_time_in_seconds = total / (n_log > 0 ? n_log : 1);
+      its[i].cumulative_time_in_seconds = total * (i + 1) / (n_log > 0 ? n_log : 1);
+    }
     if (verbose)
       std::printf("%4d  cost % .6e  change % .3e  |grad| %.3e  |step| %.3e  rho % .3e  radius %.3e  %s\n", its[i].iteration, its[i].cost,
                   its[i].cost_change, its[i].gradient_max_norm, its[i].step_norm, its[i].relative_decrease, its[i].trust_region_radius,
                   its[i].step_is_successful ? "ok" : (its[i].step_is_valid ? "rejected" : "invalid"));
   }
-  sum->initial_cost = fin.initial_cost;
-  sum->final_cost = fin.minimum_cost;
+  // pose-only mode: the constant camera's residual blocks left the program; Ceres' summary adds their cost back (0 outside the mode)
+  sum->fixed_cost = pba_internal_fixed_cost(e);
+  sum->initial_cost = fin.initial_cost + sum->fixed_cost;
+  sum->final_cost = fin.minimum_cost + sum->fixed_cost;
   sum->num_successful_steps = fin.num_successful;
   sum->num_unsuccessful_steps = fin.num_unsuccessful;
   sum->num_iterations = n_log < max_out ? n_log : max_out;
@@ -165,6 +178,57 @@ static int summarize_device_solve(pba_engine* e, const pba_solver_options* o, pb
   return PBA_OK;
 }
 
+// Host-stepped variant: one step per round trip.  Every trip computes one trust-region step with the damping of the state (and, with it,
+// cost and gradient norms of the current point), hands the step's scalar block to lm_decide and acts on the outcome: an accepted
+// candidate becomes the current point (its Jacobian pass has usually run already: the candidate pass speculates on acceptance as long
+// as steps are accepted), a rejected or invalid one makes the next trip re-solve the stored linearisation with the new damping.
+// The state lives here and the log is the caller's array, so the iteration limit is not bounded by the device log.
+static int solve_host_stepped(pba_engine* e, const pba_solver_options* o, pba_solver_summary* sum, pba_iteration_summary* its,
+                              int32_t max_out, double t_start, bool verbose) {
+  const int max_log = its ? max_out : 0;
+  pba::LmState st = pba::lm_initial_state(o, 0);      // (only the FLIPS of the parity are used here: the engine keeps its own)
+  pba_internal_reset_pass_counts(e);
+  pba_internal_set_speculate(e, 1);
+  int rc = pba_linearize(e, nullptr);
+  if (rc) return rc;
+  int64_t resolves = 0;
+  bool resolve = false;      // this trip's step is a re-solve: its predecessor was rejected or invalid
+  for (;;) {
+    const double t_trip = now();
+    // the gradient norms alone: iteration zero of a zero-iteration solve, and the point accepted by the last iteration allowed
+    const int grad_only = st.first ? o->max_num_iterations <= 0 : st.iteration >= o->max_num_iterations;
+    pba_step_info info;
+    double s[pba::kNumScal];
+    rc = pba_internal_step(e, st.radius, st.first, o, &info, s, grad_only);
+    // a non-finite residual at the linearisation point is lm_decide's to rule on (kEvalFailLin): the solve fails, the call does not
+    if (rc && rc != PBA_ERR_NUMERIC) return rc;
+    const double t_step = now() - t_trip;
+    if (resolve) ++resolves;
+    const int cur = st.cur, n0 = st.n_log;
+    pba::lm_decide(&st, s, its, max_log, grad_only);
+    const bool accepted = st.cur != cur;
+    if (accepted) {
+      pba_internal_set_speculate(e, 1);   // accepted: keep betting on acceptance
+      if ((rc = pba_accept(e))) return rc;
+      if ((rc = pba_linearize(e, nullptr))) return rc;   // no-op when the candidate pass was a Jacobian pass
+    } else if (!st.done) {
+      pba_internal_set_speculate(e, 0);   // rejected or invalid: the retry only needs the cost
+    }
+    const double t = now();
+    for (int i = n0; i < st.n_log && i < max_log; ++i) {
+      its[i].iteration_time_in_seconds = t - t_trip;
+      its[i].cumulative_time_in_seconds = t - t_start;
+      if (resolve) its[i].step_solver_time_in_seconds = t_step;
+    }
+    resolve = !accepted;
+    // the one trip after the end: the iteration limit right after an acceptance still owes that point's gradient norms
+    if (st.done && !(st.done == pba::kLmMaxIterations && !grad_only && pba::lm_final_pass_needed(&st))) break;
+  }
+  rc = summarize_solve(e, o, &st, nullptr, sum, its, max_out, t_start, verbose, -1);
+  sum->num_resolve_passes = resolves;      // the re-solves actually run (include/pba.h)
+  return rc;
+}
+
 extern "C" int pba_solve(pba_engine* e, const pba_solver_options* o, pba_solver_summary* sum, pba_iteration_summary* its,
                          int32_t max_out) {
   if (!e || !o || !sum) return PBA_ERR_INVALID;
@@ -189,179 +253,11 @@ extern "C" int pba_solve(pba_engine* e, const pba_solver_options* o, pba_solver_
   }
   sum->num_residual_blocks = (int32_t)blocks;
   sum->num_residuals = (int32_t)(blocks * pba_internal_patch_len(e));
-  sum->fixed_cost = 0.0;   // every residual block has a free point unless the points are constant (below)
   const bool verbose = o->verbose && pba_internal_rank(e) == 0;
-  if (pba_internal_async_capable(e, o)) {
-    pba_internal_reset_pass_counts(e);
-    if (pba_internal_resident_capable(e, o)) return solve_resident(e, o, sum, its, max_out, t_start, verbose);
-    return solve_async(e, o, sum, its, max_out, t_start, verbose);
-  }
-
-  int n_it = 0;
-  auto push = [&](const pba_iteration_summary& s) {
-    if (its && n_it < max_out) its[n_it] = s;
-    ++n_it;
-    if (verbose)
-      std::printf("%4d  cost % .6e  change % .3e  |grad| %.3e  |step| %.3e  rho % .3e  radius %.3e  %s\n", s.iteration, s.cost,
-                  s.cost_change, s.gradient_max_norm, s.step_norm, s.relative_decrease, s.trust_region_radius,
-                  s.step_is_successful ? "ok" : (s.step_is_valid ? "rejected" : "invalid"));
-  };
-
-  double radius = o->initial_trust_region_radius, decrease_factor = 2.0;
-  int num_consecutive_invalid = 0;
-  pba_step_info info;
-  std::memset(&info, 0, sizeof(info));
-
-  // ---- IterationZero -----------------------------------------------------------------------------------
-  double t_iter = now();
+  if (!pba_internal_async_capable(e, o)) return solve_host_stepped(e, o, sum, its, max_out, t_start, verbose);
   pba_internal_reset_pass_counts(e);
-  pba_internal_set_speculate(e, 1);
-  int rc = pba_linearize(e, nullptr);
-  if (rc) return rc;
-  bool last = o->max_num_iterations <= 0;
-  rc = pba_internal_step(e, radius, 1, o, &info, last ? 1 : 0);
-  if (rc == PBA_ERR_NUMERIC) {
-    sum->termination_type = 2;
-    std::snprintf(sum->message, sizeof(sum->message), "Initial residual and Jacobian evaluation failed.");
-    sum->total_time_in_seconds = now() - t_start;
-    return PBA_OK;
-  }
-  if (rc) return rc;
-  bool info_valid = !last;
-  double x_cost = info.cost;
-  // pose-only mode: the constant camera's residual blocks left the program; Ceres' summary adds their cost back
-  sum->fixed_cost = pba_internal_fixed_cost(e);
-  sum->initial_cost = x_cost + sum->fixed_cost;
-  double minimum_cost = x_cost;
-
-  pba_iteration_summary it;
-  std::memset(&it, 0, sizeof(it));
-  it.iteration = 0; it.eta = 1e-1;
-  it.cost = x_cost; it.gradient_max_norm = info.gradient_max_norm; it.gradient_norm = info.gradient_norm;
-  it.step_is_valid = 1; it.step_is_successful = 1;
-
-  auto finalize = [&]() -> bool {
-    // TrustRegionMinimizer::FinalizeIterationAndCheckIfMinimizerCanContinue
-    if (it.step_is_successful) {
-      ++sum->num_successful_steps;
-      if (x_cost < minimum_cost || it.iteration == 0) { minimum_cost = x_cost; it.step_is_nonmonotonic = 0; }
-      else it.step_is_nonmonotonic = 1;
-    } else {
-      ++sum->num_unsuccessful_steps;
-    }
-    it.trust_region_radius = radius;
-    const double t = now();
-    it.iteration_time_in_seconds = t - t_iter;
-    it.cumulative_time_in_seconds = t - t_start;
-    push(it);
-    if (it.iteration >= o->max_num_iterations) {
-      sum->termination_type = 1;
-      std::snprintf(sum->message, sizeof(sum->message), "Maximum number of iterations reached. Number of iterations: %d.", it.iteration);
-      return false;
-    }
-    if (it.step_is_successful && it.gradient_max_norm <= o->gradient_tolerance) {
-      sum->termination_type = 0;
-      std::snprintf(sum->message, sizeof(sum->message), "Gradient tolerance reached. Gradient max norm: %e <= %e", it.gradient_max_norm, o->gradient_tolerance);
-      return false;
-    }
-    if (radius <= o->min_trust_region_radius) {
-      sum->termination_type = 0;
-      std::snprintf(sum->message, sizeof(sum->message), "Minimum trust region radius reached. Trust region radius: %e <= %e", radius, o->min_trust_region_radius);
-      return false;
-    }
-    return true;
-  };
-  auto step_rejected = [&]() { radius = radius / decrease_factor; decrease_factor *= 2.0; };   // LM::StepRejected
-
-  while (finalize()) {
-    t_iter = now();
-    const int iteration = it.iteration + 1;
-    const double prev_gmax = it.gradient_max_norm, prev_gnorm = it.gradient_norm;
-    std::memset(&it, 0, sizeof(it));
-    it.iteration = iteration; it.eta = 1e-1;
-    it.gradient_max_norm = prev_gmax; it.gradient_norm = prev_gnorm;
-    const double t_solve = now();
-    if (!info_valid) {
-      // re-solve with the new damping from the stored linearisation (rejected / invalid predecessor)
-      rc = pba_internal_step(e, radius, 0, o, &info, 0);
-      if (rc) return rc;
-      sum->num_resolve_passes++;
-      it.step_solver_time_in_seconds = now() - t_solve;
-    }
-    info_valid = false;
-    it.linear_solver_iterations = 1;
-    it.model_cost_change = info.model_cost_change;
-    const bool step_is_valid = info.linear_solver_ok && info.model_cost_change > 0.0;
-    if (!step_is_valid) {
-      // HandleInvalidStep
-      ++num_consecutive_invalid;
-      if (num_consecutive_invalid >= o->max_num_consecutive_invalid_steps) {
-        sum->termination_type = 2;
-        std::snprintf(sum->message, sizeof(sum->message), "Number of consecutive invalid steps more than Solver::Options::max_num_consecutive_invalid_steps: %d", o->max_num_consecutive_invalid_steps);
-        it.cost = x_cost; it.trust_region_radius = radius;
-        push(it);
-        break;
-      }
-      pba_internal_set_speculate(e, 0);
-      step_rejected();
-      it.cost = x_cost;
-      continue;
-    }
-    it.step_is_valid = 1;
-    num_consecutive_invalid = 0;
-    const double candidate_cost = info.eval_ok ? info.candidate_cost : std::numeric_limits<double>::max();
-    it.candidate_cost = candidate_cost;
-    // ParameterToleranceReached
-    it.step_norm = info.step_norm;
-    const double step_size_tolerance = o->parameter_tolerance * (info.x_norm + o->parameter_tolerance);
-    if (it.step_norm <= step_size_tolerance) {
-      sum->termination_type = 0;
-      std::snprintf(sum->message, sizeof(sum->message), "Parameter tolerance reached. Relative step_norm: %e <= %e.", it.step_norm / (info.x_norm + o->parameter_tolerance), o->parameter_tolerance);
-      break;
-    }
-    // FunctionToleranceReached
-    it.cost_change = x_cost - candidate_cost;
-    if (std::fabs(it.cost_change) <= o->function_tolerance * x_cost) {
-      sum->termination_type = 0;
-      std::snprintf(sum->message, sizeof(sum->message), "Function tolerance reached. |cost_change|/cost: %e <= %e", std::fabs(it.cost_change) / x_cost, o->function_tolerance);
-      break;
-    }
-    // IsStepSuccessful
-    it.relative_decrease = it.cost_change / info.model_cost_change;
-    if (it.relative_decrease > o->min_relative_decrease) {
-      // HandleSuccessfulStep: x <- candidate, re-linearise, LM::StepAccepted
-      pba_internal_set_speculate(e, 1);   // accepted: keep betting on acceptance
-      if ((rc = pba_accept(e))) return rc;
-      if ((rc = pba_linearize(e, nullptr))) return rc;   // no-op when the candidate pass was a Jacobian pass
-      x_cost = candidate_cost;
-      radius = radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * it.relative_decrease - 1.0, 3));
-      radius = std::min(o->max_trust_region_radius, radius);
-      decrease_factor = 2.0;
-      last = iteration >= o->max_num_iterations;
-      rc = pba_internal_step(e, radius, 0, o, &info, last ? 1 : 0);
-      if (rc == PBA_ERR_NUMERIC) {
-        sum->termination_type = 2;
-        std::snprintf(sum->message, sizeof(sum->message), "Residual and Jacobian evaluation failed.");
-        break;
-      }
-      if (rc) return rc;
-      info_valid = !last;
-      it.step_is_successful = 1;
-      it.cost = x_cost;
-      it.gradient_max_norm = info.gradient_max_norm;
-      it.gradient_norm = info.gradient_norm;
-    } else {
-      // HandleUnsuccessfulStep
-      pba_internal_set_speculate(e, 0);   // rejected: the retry only needs the cost
-      step_rejected();
-      it.cost = candidate_cost;
-    }
-  }
-  pba_internal_pass_counts(e, &sum->num_jacobian_passes, &sum->num_cost_passes);
-  sum->final_cost = minimum_cost + sum->fixed_cost;
-  sum->num_iterations = n_it < max_out ? n_it : max_out;
-  sum->total_time_in_seconds = now() - t_start;
-  return PBA_OK;
+  if (pba_internal_resident_capable(e, o)) return solve_resident(e, o, sum, its, max_out, t_start, verbose);
+  return solve_async(e, o, sum, its, max_out, t_start, verbose);
 }
 
 // Batch variant of solve_async: n independent windows, one batched launch per phase on ONE stream (pba_batch.h).  Each window follows the
@@ -443,7 +339,8 @@ extern "C" int pba_solve_batch(pba_engine* const* es, int32_t n, const pba_solve
   if (rc) return rc;
   for (int w = 0; w < n; ++w) {
     const bool verbose = o[w].verbose != 0;
-    const int rcw = summarize_device_solve(es[w], &o[w], &sums[w], its ? its + (size_t)w * (size_t)max_out : nullptr, its ? max_out : 0, t_start, verbose, -1);
+    const int rcw = summarize_solve(es[w], &o[w], mirror(es[w]), pba_internal_async_log(es[w]), &sums[w],
+                                    its ? its + (size_t)w * (size_t)max_out : nullptr, its ? max_out : 0, t_start, verbose, -1);
     if (rcw) return rcw;
   }
   return PBA_OK;

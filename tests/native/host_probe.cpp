@@ -1,10 +1,12 @@
 // Test shim (NOT part of the product): C hooks over pieces of the drop-in host library that only tests call -- the Options stream
 // operator and Calibration helpers (reference src/photobundle.h:81-82, src/calibration.h:40-70), the host descriptor channels
-// (host/imgproc.h) and the pyramid helpers (host/photobundle_pyramid.h).  Links libphotobundle.so; bound through ctypes by
-// tests/test_host_api_cpu.py, tests/test_pyramid_cpu.py and tests/test_gpu_producers.py.
+// (host/imgproc.h), the pyramid helpers (host/photobundle_pyramid.h) and the trust-region rules (csrc/pba_lm_rules.h, header only: this
+// file is plain C++, so the rules run their host form here).  Links libphotobundle.so; bound through ctypes by
+// tests/test_host_api_cpu.py, tests/test_pyramid_cpu.py, tests/test_lm_rules_cpu.py and tests/test_gpu_producers.py.
 #include "../../photobundle_amd/host/photobundle.h"
 #include "../../photobundle_amd/host/photobundle_pyramid.h"
 #include "../../photobundle_amd/host/imgproc.h"
+#include "../../photobundle_amd/csrc/pba_lm_rules.h"
 
 #include <algorithm>
 #include <cstring>
@@ -63,4 +65,15 @@ extern "C" void pb_resize_bilinear_f32(const float* src, int rows, int cols, int
   std::vector<float> d;
   resizeBilinearF32(src, rows, cols, drows, dcols, d);
   std::copy(d.begin(), d.end(), dst);
+}
+
+// test hook (tests/test_lm_rules_cpu.py): block == nullptr: *state = lm_initial_state(o, 0); else one lm_decide on the 32-double scalar
+// block.  `state` is a pba::LmState (the test mirrors its layout and checks state_bytes).  Returns lm_final_pass_needed(state).
+extern "C" int pb_lm_rules(const pba_solver_options* o, void* state, int state_bytes, const double* block, int grad_only,
+                           pba_iteration_summary* log, int max_log) {
+  if (state_bytes != (int)sizeof(pba::LmState)) return -1;
+  pba::LmState* st = static_cast<pba::LmState*>(state);
+  if (!block) *st = pba::lm_initial_state(o, 0);
+  else pba::lm_decide(st, block, log, max_log, grad_only);
+  return pba::lm_final_pass_needed(st) ? 1 : 0;
 }

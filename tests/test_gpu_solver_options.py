@@ -3,8 +3,8 @@
 The cases of tests/test_oracle_solver_options.py (the oracle there is pinned to an independent dense loop at the same options) run
 on the engine through three drivers, each in a process of its own because the driver is chosen at pba_create:
   resident      PBA_RESIDENT=1   the whole solve as one cooperative launch (pba_resident.h)
-  pipelined     PBA_RESIDENT=0   the three-kernel asynchronous driver, decisions on the device (pba_kernels.h lm_decide)
-  host-stepped  PBA_ASYNC=0      the host loop of pba_lm.cpp
+  pipelined     PBA_RESIDENT=0   the three-kernel asynchronous driver, decisions on the device (pba_lm_rules.h lm_decide)
+  host-stepped  PBA_ASYNC=0      the host loop of pba_lm.cpp over the same lm_decide
 Each run asserts the driver that actually ran it.  Every driver is compared with the oracle (the tolerances of
 test_gpu_parity.py::_compare_traces), the resident driver with the pipelined one bit for bit, the host-stepped one with the
 pipelined one at the tolerances of the multi_sync comparison in test_gpu_multirank.py."""
