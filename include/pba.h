@@ -274,6 +274,18 @@ int pba_get_points_world(pba_engine* e, double* xyz);
  * whichever call comes second: the multi-rank transports, the precision-sweep flags, pba_solve_batch with such an engine (and, on
  * windows of 16..32 free cameras, what pba_set_cameras refuses there).  Switched off again the engine solves as a fresh one does. */
 int pba_set_points_constant(pba_engine* e, int32_t on);
+/* Structure-only solves.  Ceres: SetParameterBlockConstant on every camera block.  on != 0: pba_linearize / pba_step / pba_accept /
+ * pba_solve treat every camera as constant and refine the points against them; fixed_slot of pba_set_cameras has no effect.  Call
+ * order and lifetime are pba_set_points_constant's.  Semantics are Ceres' for the reduced program: its parameter blocks are the points,
+ * every residual block stays in it (summary.fixed_cost = 0, num_residual_blocks and num_residuals count every block).  The normal
+ * equations are block diagonal, one 3x3 block per point (1x1 in the inverse-depth mode) solved by an exact Cholesky, at every window
+ * shape (2..32 slots); a non-positive pivot or a non-finite step in any block gives linear_solver_ok = 0 and a zero step everywhere.
+ * Gradient norms, step_norm, x_norm and model_cost_change run over the point columns.  The cameras are never written: pba_get_state
+ * returns them byte for byte as set.  pba_solve runs the host-stepped driver.  pba_get_reduced_system returns PBA_ERR_STATE in the mode
+ * (there is no reduced camera system).  Refused with PBA_ERR_INVALID and a message, whichever call comes second: both constant modes at
+ * once (the program would be empty), the multi-rank transports, the precision-sweep flags, pba_solve_batch with such an engine (and, on
+ * windows of 16..32 free cameras, what pba_set_cameras refuses there).  Switched off again the engine solves as a fresh one does. */
+int pba_set_cameras_constant(pba_engine* e, int32_t on);
 /* Current (best) state; either pointer may be NULL. */
 int pba_get_state(pba_engine* e, double* cams6, double* xyz);
 
@@ -289,6 +301,10 @@ int pba_accept(pba_engine* e);
  * gradient-only pass that ends a solve at the iteration limit leaves them alone): n = 6 * free cameras.
  * S[n*n] row-major = s_c (U - sum W P W^T) s_c + D_c^2, rhs[n], both in Jacobi-scaled space. */
 int pba_get_reduced_system(pba_engine* e, double* S, double* rhs, int32_t* n);
+/* Test hook of the cameras-constant mode (needs pba_config.flags bit 0, after a pba_step in the mode): V9 [n_points][9] the scaled and
+ * damped point blocks s_p V_p s_p + D_p^2, row-major; rhs3 [n_points][3] the scaled gradient.  In the inverse-depth mode entry 0 of
+ * each is set and the rest are zero.  Either pointer may be NULL. */
+int pba_get_point_system(pba_engine* e, double* V9, double* rhs3);
 /* Test hook: per-observation record of the last linearisation: [n_obs][6] = rho'*M11, M12, M22, rho'*b1, b2, rho/2. */
 int pba_get_obs_records(pba_engine* e, double* rec6);
 

@@ -12,6 +12,7 @@
 #include "pba_wide.h"
 #include "pba_batch.h"
 #include "pba_pose.h"
+#include "pba_points.h"
 
 #include <algorithm>
 #include <chrono>
@@ -163,6 +164,16 @@ struct pba_engine {
   int pose_grid = 0;                // workgroups of the last k_pose_system launch (rows of d_pose_partial)
   double* d_pose_partial = nullptr; // [kPoseMaxGrid][n_frames * kPoseVals]
   double* d_pose_sums = nullptr;    // [n_frames * kPoseVals + 2]
+
+  // structure-only solves (pba_set_cameras_constant, pba_points.h): everything on first use
+  bool cams_const = false;
+  bool pts_cams_synced = false;     // both camera parities hold the same (constant) cameras and geometry
+  int pts_sys_cur = -1;             // parity whose linearisation d_pts_sys was built from, -1 none
+  bool pts_dbg_valid = false;       // d_pts_V / d_pts_rhs hold the blocks of a step in the mode
+  double* d_pts_sys = nullptr;      // [kPointsSys][n_points]
+  double* d_pts_part = nullptr;     // [waves of k_points_solve][kPointsRow]
+  double* d_pts_V = nullptr;        // [n_points][9] test hook (pba_config.flags bit 0)
+  double* d_pts_rhs = nullptr;      // [n_points][3]
 
   // batched solves (pba_solve_batch, pba_batch.h): the window table lives with the batch's FIRST engine (grow-only), whose stream
   // carries the batch; while a batch runs every engine's `stream` names that stream and `stream_own` keeps its own
@@ -893,6 +904,7 @@ void pba_destroy(pba_engine* e) {
   dev_free(&e->d_log);
   dev_free(&e->d_res_sync);
   dev_free(&e->d_pose_partial); dev_free(&e->d_pose_sums);
+  dev_free(&e->d_pts_sys); dev_free(&e->d_pts_part); dev_free(&e->d_pts_V); dev_free(&e->d_pts_rhs);
   dev_free(&e->d_wfac); dev_free(&e->d_wpt_part); dev_free(&e->d_went); dev_free(&e->d_wchunk); dev_free(&e->d_wpair_chunk); dev_free(&e->d_wsums);
   for (int k = 0; k < 2 * pba_engine::kEvPairs; ++k) if (e->ev[k]) (void)hipEventDestroy(e->ev[k]);
   if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -1362,6 +1374,8 @@ int pba_set_problem(pba_engine* e, int32_t n_points, const double* xyz, const do
   e->inverse_depth = false;         // back to the reference's free world points until pba_set_inverse_depth says otherwise
   e->points_const = false;          // ... and to free points until pba_set_points_constant says otherwise
   e->pose_xyz_synced = false; e->pose_sums_cur = -1;
+  e->cams_const = false;            // ... and to free cameras until pba_set_cameras_constant says otherwise
+  e->pts_cams_synced = false; e->pts_sys_cur = -1; e->pts_dbg_valid = false;
   e->have_lin = false;
   e->lin_valid[0] = e->lin_valid[1] = false;
   return PBA_OK;
@@ -1425,6 +1439,7 @@ int pba_set_cameras(pba_engine* e, const double* cams6, int32_t n_frames, int32_
   e->have_lin = false;
   e->lin_valid[0] = e->lin_valid[1] = false;
   e->pose_sums_cur = -1;
+  e->pts_cams_synced = false; e->pts_sys_cur = -1; e->pts_dbg_valid = false;
   return PBA_OK;
 }
 
@@ -1475,6 +1490,7 @@ int pba_set_inverse_depth(pba_engine* e, const double* rays6, const double* rho)
   e->have_lin = false;
   e->lin_valid[0] = e->lin_valid[1] = false;
   e->pose_xyz_synced = false; e->pose_sums_cur = -1;
+  e->pts_sys_cur = -1; e->pts_dbg_valid = false;
   return PBA_OK;
 }
 
@@ -1492,6 +1508,8 @@ int pba_set_points_constant(pba_engine* e, int32_t on) {
   if (on) {
     const char* why = pose_refusal(e);
     if (why) return fail(e, PBA_ERR_INVALID, "pba_set_points_constant: %s", why);
+    if (e->cams_const)
+      return fail(e, PBA_ERR_INVALID, "pba_set_points_constant: the cameras-constant mode (pba_set_cameras_constant) is on: with every block constant the program is empty");
   }
   e->points_const = on != 0;
   e->pose_xyz_synced = false; e->pose_sums_cur = -1;
@@ -1506,6 +1524,39 @@ static int pose_sync_points(pba_engine* e) {
   if (e->pose_xyz_synced) return PBA_OK;
   HIP_TRY(e, hipMemcpyAsync(e->d_xyz[1 - e->cur], e->d_xyz[e->cur], sizeof(double) * 3 * e->n_points, hipMemcpyDeviceToDevice, e->stream));
   e->pose_xyz_synced = true;
+  return PBA_OK;
+}
+
+// Why the structure-only mode cannot run with what the engine has been given (nullptr: it can)
+static const char* points_refusal(const pba_engine* e) {
+  if (e->points_const) return "the points-constant mode (pba_set_points_constant) is on: with every block constant the program is empty";
+  if (e->comm.multi()) return "multi-rank solves (pba_comm_*) are not built for the cameras-constant mode";
+  if ((e->cfg.flags >> 1) & 3) return "the precision-sweep sampler modes (pba_config.flags bits 1-2) are not built for the cameras-constant mode";
+  return nullptr;
+}
+
+int pba_set_cameras_constant(pba_engine* e, int32_t on) {
+  if (!e) return PBA_ERR_INVALID;
+  if (!e->have_problem) return fail(e, PBA_ERR_STATE, "call order violated: pba_set_cameras_constant before pba_set_problem");
+  PBA_NOT_POISONED(e);
+  if (on) {
+    const char* why = points_refusal(e);
+    if (why) return fail(e, PBA_ERR_INVALID, "pba_set_cameras_constant: %s", why);
+  }
+  e->cams_const = on != 0;
+  e->pts_cams_synced = false; e->pts_sys_cur = -1; e->pts_dbg_valid = false;
+  e->have_lin = false;
+  e->lin_valid[0] = e->lin_valid[1] = false;
+  return PBA_OK;
+}
+
+// The constant cameras and their geometry live in BOTH parities (the candidate pass reads the candidate parity, pba_accept flips it):
+// device-to-device copies of the current ones, byte for byte, once per problem.
+static int points_sync_cameras(pba_engine* e) {
+  if (e->pts_cams_synced) return PBA_OK;
+  HIP_TRY(e, hipMemcpyAsync(e->d_cams[1 - e->cur], e->d_cams[e->cur], sizeof(double) * 6 * e->n_frames, hipMemcpyDeviceToDevice, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(e->d_geom[1 - e->cur], e->d_geom[e->cur], sizeof(CamGeom) * e->n_frames, hipMemcpyDeviceToDevice, e->stream));
+  e->pts_cams_synced = true;
   return PBA_OK;
 }
 
@@ -1531,8 +1582,10 @@ int pba_linearize(pba_engine* e, double* cost) {
   PBA_NOT_POISONED(e);
   HIP_TRY(e, hipSetDevice(e->cfg.device));
   if (e->points_const) { const int rcp = pose_sync_points(e); if (rcp) return rcp; }
+  if (e->cams_const) { const int rcp = points_sync_cameras(e); if (rcp) return rcp; }
   if (!e->lin_valid[e->cur]) {
     if (e->pose_sums_cur == e->cur) e->pose_sums_cur = -1;
+    if (e->pts_sys_cur == e->cur) e->pts_sys_cur = -1;
     SampleParams sp = make_sample_params(e, e->cur);
     ev_begin(e, 0);
     launch_sample<true>(e, sp);
@@ -1681,6 +1734,63 @@ static int pose_step(pba_engine* e, double radius, int32_t init_scale, const pba
   return wait_step_scalars(e, seq, out, scal);
 }
 
+// pba_step of the structure-only mode (pba_points.h): per-point blocks of the stored linearisation (once per linearisation), the
+// block-diagonal damped solve into the candidate points, the candidate pass there with the unchanged cameras, the scalar block.
+static int points_step(pba_engine* e, double radius, int32_t init_scale, const pba_solver_options* o, pba_step_info* out, double* scal,
+                       int grad_only) {
+  const int cur = e->cur, cand = 1 - e->cur;
+  const int grid = (e->n_points + kPointsThreads - 1) / kPointsThreads;
+  const bool dbg = (e->cfg.flags & 1) != 0;
+  int rc;
+  if ((rc = points_sync_cameras(e))) return rc;
+  if ((rc = dev_alloc(e, &e->d_pts_sys, (size_t)kPointsSys * e->n_points))) return rc;
+  if ((rc = dev_alloc(e, &e->d_pts_part, (size_t)grid * kPointsWaves * kPointsRow))) return rc;
+  if (dbg) {
+    if ((rc = dev_alloc(e, &e->d_pts_V, (size_t)9 * e->n_points))) return rc;
+    if ((rc = dev_alloc(e, &e->d_pts_rhs, (size_t)3 * e->n_points))) return rc;
+  }
+  if (e->pts_sys_cur != cur) {
+    PointsSystemParams ps{};
+    ps.xyz = e->d_xyz[cur]; ps.rays = e->inverse_depth ? e->d_rays : nullptr; ps.geom = e->d_geom[cur]; ps.rec = e->d_rec[cur];
+    ps.pt_begin = e->d_pt_begin; ps.obs_slot = e->d_obs_slot; ps.sys = e->d_pts_sys; ps.rec_stride = e->rec_stride;
+    ps.n_points = e->n_points; ps.n_frames = e->n_frames; ps.fx = e->cfg.fx; ps.fy = e->cfg.fy;
+    ev_begin(e, 2);
+    hipLaunchKernelGGL(k_points_system, dim3(grid), dim3(kPointsThreads), 0, e->stream, ps);
+    ev_end(e, 2);
+    HIP_TRY(e, hipGetLastError());
+    e->pts_sys_cur = cur;
+  }
+  PointsSolveParams so{};
+  so.sys = e->d_pts_sys; so.xyz = e->d_xyz[cur]; so.xyz_cand = e->d_xyz[cand]; so.sp = e->d_sp; so.part = e->d_pts_part;
+  so.V_dbg = dbg ? e->d_pts_V : nullptr; so.rhs_dbg = dbg ? e->d_pts_rhs : nullptr;
+  so.n_points = e->n_points; so.dim = e->inverse_depth ? 1 : 3; so.init_scale = init_scale; so.jacobi = o->jacobi_scaling;
+  so.grad_only = grad_only; so.radius = radius; so.min_diag = o->min_lm_diagonal; so.max_diag = o->max_lm_diagonal;
+  ev_begin(e, 3);
+  hipLaunchKernelGGL(k_points_solve, dim3(grid), dim3(kPointsThreads), 0, e->stream, so);
+  ev_end(e, 3);
+  HIP_TRY(e, hipGetLastError());
+  if (dbg && !(grad_only && !init_scale)) e->pts_dbg_valid = true;
+  const unsigned long long seq = ++e->seq;
+  PointsFinalizeParams fp{};
+  fp.part = e->d_pts_part; fp.n_rows = grid * kPointsWaves; fp.cost_lin = e->d_block_cost[cur]; fp.fail_lin = e->d_block_fail[cur];
+  fp.n_lin = e->cost_blocks[cur]; fp.scal = e->d_scal; fp.host_scal = e->h_scal_dev; fp.host_seq = host_seq_dev(e); fp.seq = seq;
+  if (!grad_only) {
+    // candidate point: Jacobian pass when speculating on acceptance, else cost pass; the cameras are the current ones
+    SampleParams sp = make_sample_params(e, cand);
+    candidate_pass(e, sp, cand, false);
+    fp.cost_cand = e->d_block_cost[cand]; fp.fail_cand = e->d_block_fail[cand]; fp.n_cand = e->sample_grid;
+  }
+  hipLaunchKernelGGL(k_points_finalize, dim3(1), dim3(kPointsThreads), 0, e->stream, fp);
+  HIP_TRY(e, hipGetLastError());
+  rc = wait_step_scalars(e, seq, out, scal);
+  if ((rc == PBA_OK || rc == PBA_ERR_NUMERIC) && !grad_only && !out->linear_solver_ok) {
+    // a failed block makes the whole step a zero step: the candidate points are the current ones again
+    HIP_TRY(e, hipMemcpyAsync(e->d_xyz[cand], e->d_xyz[cur], sizeof(double) * 3 * e->n_points, hipMemcpyDeviceToDevice, e->stream));
+    e->lin_valid[cand] = false;
+  }
+  return rc;
+}
+
 int pba_step(pba_engine* e, double radius, int32_t init_scale, const pba_solver_options* o, pba_step_info* out) {
   return pba_internal_step(e, radius, init_scale, o, out, nullptr, 0);
 }
@@ -1695,6 +1805,7 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
   PBA_NOT_POISONED(e);
   HIP_TRY(e, hipSetDevice(e->cfg.device));
   if (e->points_const) return pose_step(e, radius, init_scale, o, out, scal, grad_only);
+  if (e->cams_const) return points_step(e, radius, init_scale, o, out, scal, grad_only);
   const int cur = e->cur, cand = 1 - e->cur;
   const int n = 6 * e->n_free;
   const bool multi = e->comm.multi();
@@ -1776,12 +1887,27 @@ int pba_accept(pba_engine* e) {
   e->cur = 1 - e->cur;
   e->have_lin = e->lin_valid[e->cur];
   e->pose_sums_cur = -1;
+  e->pts_sys_cur = -1;
+  return PBA_OK;
+}
+
+int pba_get_point_system(pba_engine* e, double* V9, double* rhs3) {
+  if (!e) return PBA_ERR_INVALID;
+  if (!(e->cfg.flags & 1)) return fail(e, PBA_ERR_STATE, "call order violated: pba_get_point_system needs pba_config.flags bit 0 (keep reduced system)");
+  if (!e->cams_const || !e->pts_dbg_valid)
+    return fail(e, PBA_ERR_STATE, "call order violated: pba_get_point_system needs a pba_step in the cameras-constant mode (pba_set_cameras_constant)");
+  PBA_NOT_POISONED(e);
+  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  if (V9) HIP_TRY(e, hipMemcpyAsync(V9, e->d_pts_V, sizeof(double) * 9 * e->n_points, hipMemcpyDeviceToHost, e->stream));
+  if (rhs3) HIP_TRY(e, hipMemcpyAsync(rhs3, e->d_pts_rhs, sizeof(double) * 3 * e->n_points, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
   return PBA_OK;
 }
 
 int pba_get_reduced_system(pba_engine* e, double* S, double* rhs, int32_t* n_out) {
   if (!e || !n_out) return PBA_ERR_INVALID;
   if (!(e->cfg.flags & 1)) return fail(e, PBA_ERR_STATE, "call order violated: pba_get_reduced_system needs pba_config.flags bit 0 (keep reduced system)");
+  if (e->cams_const) return fail(e, PBA_ERR_STATE, "pba_get_reduced_system: the cameras-constant mode (pba_set_cameras_constant) has no reduced camera system; see pba_get_point_system");
   PBA_NOT_POISONED(e);
   HIP_TRY(e, hipSetDevice(e->cfg.device));
   const int n = 6 * e->n_free;
@@ -1813,6 +1939,8 @@ int pba_comm_init_rccl(pba_engine* e, const void* id128, int32_t rank, int32_t w
     return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for wide windows (%d free cameras)", e->n_free);
   if (world > 1 && e->points_const)
     return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for the points-constant mode (pba_set_points_constant)");
+  if (world > 1 && e->cams_const)
+    return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for the cameras-constant mode (pba_set_cameras_constant)");
   PBA_NOT_POISONED(e);
   HIP_TRY(e, hipSetDevice(e->cfg.device));
   if (e->comm.init_rccl(id128, rank, world)) return fail(e, PBA_ERR_COMM, "%s", e->comm.err.c_str());
@@ -1825,6 +1953,8 @@ int pba_comm_init_callback(pba_engine* e, pba_allreduce_fn fn, void* ctx, int32_
     return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for wide windows (%d free cameras)", e->n_free);
   if (world > 1 && e->points_const)
     return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for the points-constant mode (pba_set_points_constant)");
+  if (world > 1 && e->cams_const)
+    return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for the cameras-constant mode (pba_set_cameras_constant)");
   PBA_NOT_POISONED(e);
   HIP_TRY(e, hipSetDevice(e->cfg.device));
   if (e->comm.init_callback(fn, ctx, rank, world)) return fail(e, PBA_ERR_COMM, "%s", e->comm.err.c_str());
@@ -1959,7 +2089,7 @@ int64_t pba_internal_local_blocks(const pba_engine* e) { return e->n_obs; }
 int pba_internal_patch_len(const pba_engine* e) { return e->channels * (2 * e->cfg.radius + 1) * (2 * e->cfg.radius + 1); }
 // ---- asynchronous driver ----------------------------------------------------------------------------------------
 int pba_internal_async_capable(const pba_engine* e, const pba_solver_options* o) {
-  if (e->points_const) return 0;     // the pose-only mode is built on the host-stepped driver
+  if (e->points_const || e->cams_const) return 0;     // the pose-only and structure-only modes are built on the host-stepped driver
   return e->use_async && fused_capable(e) && (e->comm.kind != 2 || e->comm.peer) && o->max_num_iterations < pba_engine::kMaxLog - 2 && !e->profile;
 }
 int pba_internal_points_constant(const pba_engine* e) { return e->points_const ? 1 : 0; }
@@ -2382,6 +2512,7 @@ int pba_internal_batch_validate(pba_engine* const* es, int32_t n, const pba_solv
     if (e->wide || e->n_free > kMaxFrames - 1) return batch_refuse(es, i, PBA_ERR_INVALID, "wide window (%d free cameras, a batch takes <= %d)", e->n_free, kMaxFrames - 1);
     if ((e->cfg.flags >> 1) & 3) return batch_refuse(es, i, PBA_ERR_INVALID, "the precision-sweep flags solve alone");
     if (e->points_const) return batch_refuse(es, i, PBA_ERR_INVALID, "the points-constant mode (pba_set_points_constant) solves alone");
+    if (e->cams_const) return batch_refuse(es, i, PBA_ERR_INVALID, "the cameras-constant mode (pba_set_cameras_constant) solves alone");
     if (e->profile || e->stamps) return batch_refuse(es, i, PBA_ERR_INVALID, "profiling is on (pba_set_profiling / pba_reset_counters)");
     if (!pba_internal_async_capable(e, &o[i]) || e->solve_kind != 0)
       return batch_refuse(es, i, PBA_ERR_INVALID, "the options or the environment need the host-stepped driver (max_num_iterations %d)", o[i].max_num_iterations);

@@ -207,6 +207,11 @@ class Engine:
         set_problem / load; set_problem switches it off again."""
         self._check(self._L.pba_set_points_constant(self._h, 1 if on else 0), "pba_set_points_constant")
 
+    def set_cameras_constant(self, on=True):
+        """Structure-only mode (include/pba.h): every camera is held constant, the points are refined against them.  Call after
+        set_problem / load; set_problem switches it off again."""
+        self._check(self._L.pba_set_cameras_constant(self._h, 1 if on else 0), "pba_set_cameras_constant")
+
     def get_points_world(self):
         xyz = np.zeros((self.n_points, 3))
         self._check(self._L.pba_get_points_world(self._h, _ptr(xyz)), "pba_get_points_world")
@@ -241,6 +246,13 @@ class Engine:
         self._check(self._L.pba_get_reduced_system(self._h, _ptr(S), _ptr(rhs), C.byref(n)), "pba_get_reduced_system")
         assert n.value == nn
         return S, rhs
+
+    def point_system(self):
+        """Scaled and damped point blocks V [n, 3, 3] and scaled gradient rhs [n, 3] of the last step in the cameras-constant mode."""
+        V = np.zeros((self.n_points, 3, 3))
+        rhs = np.zeros((self.n_points, 3))
+        self._check(self._L.pba_get_point_system(self._h, _ptr(V), _ptr(rhs)), "pba_get_point_system")
+        return V, rhs
 
     def obs_records(self):
         rec = np.zeros((self.n_obs, 6))

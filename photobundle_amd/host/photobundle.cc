@@ -168,7 +168,8 @@ PhotometricBundleAdjustment::Options::Options(const utils::ConfigFile& cf)
       descriptorType(DescriptorTypeFromString(cf.get<std::string>("descriptorType", "Intensity"))),
       numThreads(cf.get<int>("numThreads", -1)),
       verbose((bool)cf.get<int>("verbose", 1)),
-      device(cf.get<int>("device", 0)) {}
+      device(cf.get<int>("device", 0)),
+      camerasConstant((bool)cf.get<int>("camerasConstant", 0)) {}
 
 std::ostream& operator<<(std::ostream& os, const PhotometricBundleAdjustment::Options& o) {
   using DT = PhotometricBundleAdjustment::Options::DescriptorType;
@@ -177,7 +178,8 @@ std::ostream& operator<<(std::ostream& os, const PhotometricBundleAdjustment::Op
      << "\nmaxFrameDistance = " << o.maxFrameDistance << "\nminScore = " << o.minScore << "\nminValidDepth = " << o.minValidDepth
      << "\nmaxValidDepth = " << o.maxValidDepth << "\nslidingWindowSize = " << o.slidingWindowSize << "\npatchRadius = " << o.patchRadius
      << "\ndoGaussianWeighting = " << (o.doGaussianWeighting ? 1 : 0) << "\nrobustThreshold = " << o.robustThreshold
-     << "\ndescriptorType = " << dt << "\nnumThreads = " << o.numThreads << "\nverbose = " << (o.verbose ? 1 : 0) << "\ndevice = " << o.device << "\n";
+     << "\ndescriptorType = " << dt << "\nnumThreads = " << o.numThreads << "\nverbose = " << (o.verbose ? 1 : 0) << "\ndevice = " << o.device
+     << "\ncamerasConstant = " << (o.camerasConstant ? 1 : 0) << "\n";
   return os;
 }
 
@@ -719,6 +721,7 @@ bool PhotometricBundleAdjustment::optimizeAssemble(OptimizeState& st) {
     const bool first_in_bundle = std::find(obs_slot.begin(), obs_slot.end(), first_slot) != obs_slot.end();
     if (!first_in_bundle) std::fprintf(stderr, "first camera is not in bundle\n");
     check(_engine, pba_set_cameras(_engine, cams.data(), window, first_slot), "pba_set_cameras");
+    if (_options_ptr->camerasConstant) check(_engine, pba_set_cameras_constant(_engine, 1), "pba_set_cameras_constant");
     st.lap(2);
     pba_default_solver_options(&st.so);     // GetSolverOptions (:738-761)
     st.so.verbose = _options_ptr->verbose ? 1 : 0;
@@ -745,11 +748,15 @@ void PhotometricBundleAdjustment::optimizeFinish(OptimizeState& st, Result* resu
       std::printf("pba_solve: %s  initial %.6e  final %.6e  iterations %d (successful %d)  %.3f s\n", summary.message,
                   summary.initial_cost, summary.final_cost, summary.num_iterations, summary.num_successful_steps,
                   summary.total_time_in_seconds);
-    check(_engine, pba_get_state(_engine, cams.data(), xyz.data()), "pba_get_state");
+    // (camerasConstant: the poses did not move, so the trajectory is left as it is -- no parameter round trip)
+    const bool cams_const = _options_ptr->camerasConstant;
+    check(_engine, pba_get_state(_engine, cams_const ? nullptr : cams.data(), xyz.data()), "pba_get_state");
     for (size_t i = 0; i < selected.size(); ++i) for (int k = 0; k < 3; ++k) selected[i]->X[k] = xyz[3 * i + k];
     // put back the refined camera poses (:841-844)
-    for (uint32_t id = frame_id_start; id <= frame_id_end; ++id)
-      _trajectory.atId((int)id) = ParamsToPose(&cams[6 * (id % window)]).inverse();
+    if (!cams_const) {
+      for (uint32_t id = frame_id_start; id <= frame_id_end; ++id)
+        _trajectory.atId((int)id) = ParamsToPose(&cams[6 * (id % window)]).inverse();
+    }
   }
 
   lap_o(4);

@@ -120,6 +120,9 @@ class PhotometricBundleAdjustment {
     int numThreads = -1;              // accepted for source compatibility; the solve runs on the GPU
     bool verbose = true;
     int device = 0;                   // HIP device ordinal (new)
+    // structure-only refinement (new): every camera is a constant parameter block (pba_set_cameras_constant), the optimisation
+    // refines the scene points against the trajectory exactly as the inputs chained it
+    bool camerasConstant = false;
 
     Options() {}
     Options(const utils::ConfigFile& cf);
