@@ -5,6 +5,7 @@
 // fails with PBA_ERR_NO_DEVICE when no GPU is visible.
 #include "../../include/pba.h"
 #include "pba_comm.h"
+#include "pba_handle.h"
 #include "pba_internal.h"
 #include "pba_kernels.h"
 #include "pba_frontend.h"
@@ -17,20 +18,16 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <unordered_map>
 #include <string>
 #include <vector>
 
 using namespace pba;
 
-struct pba_engine {
+struct pba_engine : pba::Handle {      // (device, stream, err, mem, events)
   pba_config cfg{};
-  hipStream_t stream = nullptr;
-  std::string err;
 
   // frames
   uint32_t* d_frames = nullptr;     // [max_frames][rows*cols] packed texels
@@ -42,7 +39,6 @@ struct pba_engine {
   uint8_t* h_img_stage = nullptr;   // pinned host copy of the frame being uploaded
   double* h_state_stage = nullptr;  // pinned, host-mapped landing buffer of pba_get_state (grown on demand)
   double* h_state_dev = nullptr;    // its device address
-  size_t h_state_cap = 0;           // doubles
   hipEvent_t ev_img_stage = nullptr;
   bool img_stage_busy = false;
   hipEvent_t ev_xdep = nullptr;     // orders another engine's stream against this one (pba_set_frame_pyr_down)
@@ -56,7 +52,6 @@ struct pba_engine {
   pba_candidate* d_fe_cand = nullptr;   // [rows*cols]
   char* d_fe_io = nullptr;          // grow-only device scratch of the visibility / descriptor calls
   char* h_fe_io = nullptr;          // pinned staging (grow-only)
-  size_t h_fe_cap = 0;
   bool fe_mask_valid = false;       // pba_frontend_visibility ran for the current frame
   int fe_n_cand = 0;
   std::vector<uint8_t> frame_set;
@@ -140,7 +135,8 @@ struct pba_engine {
   double tick_hz = 1e8;             // rate of s_memrealtime (hipDeviceAttributeWallClockRate; 100 MHz on gfx950): device-side time-outs
   bool poisoned = false;            // a publication wait timed out: the stream still holds the stalled work, every later
                                     // call fails fast and pba_destroy neither waits for the stream nor for the collective
-  unsigned long long* d_dbg = nullptr;   // PBA_SCHUR_TIMING diagnostics
+  unsigned long long* d_dbg = nullptr;   // PBA_SCHUR_TIMING diagnostics, on first use
+  static constexpr size_t kDbgWords = 8 * (1024 + 4096);
   int dbg_left = 0;
   int n_pairs = 0, part_stride = 0;
   static constexpr int kChunks = 32;
@@ -179,7 +175,6 @@ struct pba_engine {
   // carries the batch; while a batch runs every engine's `stream` names that stream and `stream_own` keeps its own
   BatchWindow* d_batch = nullptr;
   BatchWindow* h_batch = nullptr;   // pinned staging of the table
-  int batch_cap = 0;                // windows
   hipStream_t stream_own = nullptr;
   int batch_init2 = 0;              // init_scale of this window's final pass (max_num_iterations <= 0)
 
@@ -193,32 +188,20 @@ struct pba_engine {
   hipEvent_t ev[2 * kEvPairs] = {};
   bool ev_used[kEvPairs] = {};
   pba_counters ctr{};
-  std::unordered_map<void*, size_t> dev_cap;   // capacity in bytes of every dev_alloc'ed buffer, keyed by its owner field
 };
 
 namespace {
 
 double wall_seconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-int fail(pba_engine* e, int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  if (e) e->err = buf;
-  return code;
-}
-
-#define HIP_TRY(e, call)                                                                         \
-  do {                                                                                           \
-    hipError_t _r = (call);                                                                      \
-    if (_r != hipSuccess) return fail((e), PBA_ERR_HIP, "%s: %s", #call, hipGetErrorString(_r)); \
-  } while (0)
+#define HIP_TRY(e, call) PBA_HIP_TRY(e, call)
 
 // A timed-out publication wait leaves the stream stalled: every later call returns at once instead of hanging on it.
 #define PBA_NOT_POISONED(e) \
   do { if ((e)->poisoned) return fail((e), PBA_ERR_STATE, "the engine is unusable after a timed-out step (stalled stream / collective); destroy it"); } while (0)
+// ... and every call that touches the device selects the engine's first
+#define PBA_ENTER(e) \
+  do { PBA_NOT_POISONED(e); HIP_TRY(e, hipSetDevice((e)->cfg.device)); } while (0)
 
 // A peer-exchange wait that timed out on the device (k_peer_allreduce / the solve's prologue) reports through a host-mapped
 // word.  The report is STICKY: the sums of that step were poisoned (NaN) on the device, the exchange sequence numbers may no
@@ -231,23 +214,20 @@ int comm_failed(pba_engine* e) {
   return fail(e, PBA_ERR_COMM, "peer exchange timed out after %.0f s waiting for rank %u", 0.5 * e->wait_timeout_s, w - 1);
 }
 
-// Grow-only device buffers: a sliding-window caller re-submits a problem of similar size for every frame, and a
-// hipFree + hipMalloc pair per buffer per frame is pure overhead.  Contents are undefined after the call (every user
-// overwrites or uploads the whole buffer).
+// Grow-only buffers (Allocations::reserve): a sliding-window caller re-submits a problem of similar size for every frame, and a free +
+// allocate pair per buffer per frame is pure overhead.  Contents are undefined after the call (every user overwrites or uploads the
+// whole buffer).  The call is all a buffer needs besides its field: pba_destroy releases whatever the registry holds.
 template <class T>
 int dev_alloc(pba_engine* e, T** p, size_t n) {
-  if (n == 0) n = 1;
-  const size_t bytes = n * sizeof(T);
-  auto it = e->dev_cap.find(static_cast<void*>(p));
-  if (*p && it != e->dev_cap.end() && it->second >= bytes) return PBA_OK;
-  if (*p) { (void)hipFree(*p); *p = nullptr; }
-  const size_t want = bytes + bytes / 8;            // a little headroom against frame-to-frame jitter
-  HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(p), want));
-  e->dev_cap[static_cast<void*>(p)] = want;
+  HIP_TRY(e, (hipError_t)e->mem.reserve(p, MemKind::device, n));
   return PBA_OK;
 }
+// ... of pinned host memory; dev_view: host-mapped, *dev_view its device address
 template <class T>
-void dev_free(T** p) { if (*p) { (void)hipFree(*p); *p = nullptr; } }
+int host_alloc(pba_engine* e, T** p, size_t n, T** dev_view = nullptr) {
+  HIP_TRY(e, (hipError_t)e->mem.reserve(p, dev_view ? MemKind::mapped : MemKind::pinned, n, dev_view));
+  return PBA_OK;
+}
 
 // Call-order / consistency check before any pass touches the device (include/pba.h: PBA_ERR_STATE).
 int check_ready(pba_engine* e, const char* who) {
@@ -759,16 +739,6 @@ void pba_default_solver_options(pba_solver_options* o) {
   o->verbose = 0;
 }
 
-static int ensure_state_stage(pba_engine* e, size_t doubles) {
-  if (e->h_state_cap >= doubles) return PBA_OK;
-  if (e->h_state_stage) { (void)hipHostFree(e->h_state_stage); e->h_state_stage = nullptr; e->h_state_cap = 0; }
-  const size_t want = doubles + doubles / 8;
-  HIP_TRY(e, hipHostMalloc(reinterpret_cast<void**>(&e->h_state_stage), sizeof(double) * want, hipHostMallocMapped));
-  HIP_TRY(e, hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_state_dev), e->h_state_stage, 0));
-  e->h_state_cap = want;
-  return PBA_OK;
-}
-
 int pba_create(const pba_config* cfg, pba_engine** out) {
   if (!cfg || !out) return PBA_ERR_INVALID;
   *out = nullptr;
@@ -779,23 +749,18 @@ int pba_create(const pba_config* cfg, pba_engine** out) {
       (int64_t)cfg->rows * cfg->cols * cfg->max_frames * std::max(1, cfg->channels) >= (1ll << 31))
     return PBA_ERR_INVALID;
   if (cfg->channels > 1 && ((cfg->flags >> 1) & 3) != 0) return PBA_ERR_INVALID;   // the sweep modes are single-channel
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || cfg->device < 0 || cfg->device >= n_dev) {
-    (void)hipGetLastError();
-    return PBA_ERR_NO_DEVICE;
-  }
+  if (!device_exists(cfg->device)) return PBA_ERR_NO_DEVICE;
   pba_engine* e = new pba_engine();
   e->cfg = *cfg;
   int rc = PBA_OK;
   auto bail = [&](int code) { pba_destroy(e); return code; };
-  if (hipSetDevice(cfg->device) != hipSuccess) return bail(PBA_ERR_HIP);
-  if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) return bail(PBA_ERR_HIP);
+  if ((rc = handle_open(e, cfg->device))) return bail(rc);
   e->comm.stream = e->stream;
   const size_t npix = (size_t)cfg->rows * cfg->cols;
   if ((rc = dev_alloc(e, &e->d_frames, npix * cfg->max_frames))) return bail(rc);
   if ((rc = dev_alloc(e, &e->d_img_stage, npix))) return bail(rc);
-  if (hipHostMalloc(reinterpret_cast<void**>(&e->h_img_stage), npix, hipHostMallocDefault) != hipSuccess) return bail(PBA_ERR_HIP);
-  if (hipEventCreateWithFlags(&e->ev_img_stage, hipEventDisableTiming) != hipSuccess) return bail(PBA_ERR_HIP);
+  if ((rc = host_alloc(e, &e->h_img_stage, npix))) return bail(rc);
+  if ((rc = handle_event(e, &e->ev_img_stage, hipEventDisableTiming))) return bail(rc);
   if (hipMemsetAsync(e->d_frames, 0, npix * cfg->max_frames * sizeof(uint32_t), e->stream) != hipSuccess) return bail(PBA_ERR_HIP);
   e->channels = std::max(1, cfg->channels);
   if (e->channels > 1) {
@@ -815,9 +780,8 @@ int pba_create(const pba_config* cfg, pba_engine** out) {
   if ((rc = dev_alloc(e, &e->d_S, (size_t)36 * mf * mf))) return bail(rc);
   if ((rc = dev_alloc(e, &e->d_rhs, (size_t)6 * mf))) return bail(rc);
   if (hipMemsetAsync(e->d_scal, 0, kNumScal * sizeof(double), e->stream) != hipSuccess) return bail(PBA_ERR_HIP);
-  if (hipHostMalloc(reinterpret_cast<void**>(&e->h_scal), (kNumScal + 1) * sizeof(double), hipHostMallocMapped) != hipSuccess) return bail(PBA_ERR_HIP);
+  if ((rc = host_alloc(e, &e->h_scal, (size_t)kNumScal + 1, &e->h_scal_dev))) return bail(rc);
   std::memset(e->h_scal, 0, (kNumScal + 1) * sizeof(double));
-  if (hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_scal_dev), e->h_scal, 0) != hipSuccess) return bail(PBA_ERR_HIP);
   if (const char* sv = getenv("PBA_SPECULATE")) e->speculate = atoi(sv) != 0;
   if (const char* sv = getenv("PBA_FUSE")) e->fuse = atoi(sv) != 0;
   if (const char* sv = getenv("PBA_ASYNC")) e->use_async = atoi(sv) != 0;
@@ -830,10 +794,8 @@ int pba_create(const pba_config* cfg, pba_engine** out) {
   if (const char* sv = getenv("PBA_WAIT_TIMEOUT_S")) { const double v = atof(sv); if (v > 0.0) e->wait_timeout_s = v; }
   { int khz = 0; if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, cfg->device) == hipSuccess && khz > 0) e->tick_hz = 1e3 * khz; }
   if ((rc = dev_alloc(e, &e->d_lm, (size_t)1))) return bail(rc);
-  if (hipHostMalloc(reinterpret_cast<void**>(&e->h_lm), sizeof(LmState), hipHostMallocMapped) != hipSuccess) return bail(PBA_ERR_HIP);
-  if (hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_lm_dev), e->h_lm, 0) != hipSuccess) return bail(PBA_ERR_HIP);
-  if (hipHostMalloc(reinterpret_cast<void**>(&e->h_log), sizeof(pba_iteration_summary) * pba_engine::kMaxLog, hipHostMallocMapped) != hipSuccess) return bail(PBA_ERR_HIP);
-  if (hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_log_dev), e->h_log, 0) != hipSuccess) return bail(PBA_ERR_HIP);
+  if ((rc = host_alloc(e, &e->h_lm, (size_t)1, &e->h_lm_dev))) return bail(rc);
+  if ((rc = host_alloc(e, &e->h_log, (size_t)pba_engine::kMaxLog, &e->h_log_dev))) return bail(rc);
   if ((rc = dev_alloc(e, &e->d_log, (size_t)pba_engine::kMaxLog))) return bail(rc);
   if (const char* sv = getenv("PBA_SCHUR_TIMING")) {
     if (PBA_PHASE_TIMING) e->dbg_left = atoi(sv);
@@ -841,17 +803,16 @@ int pba_create(const pba_config* cfg, pba_engine** out) {
   }
   if ((rc = dev_alloc(e, &e->d_ticket, (size_t)1))) return bail(rc);
   if (hipMemsetAsync(e->d_ticket, 0, sizeof(unsigned int), e->stream) != hipSuccess) return bail(PBA_ERR_HIP);
-  if (hipHostMalloc(reinterpret_cast<void**>(&e->h_comm_err), sizeof(unsigned int), hipHostMallocMapped) != hipSuccess) return bail(PBA_ERR_HIP);
+  if ((rc = host_alloc(e, &e->h_comm_err, (size_t)1, &e->h_comm_err_dev))) return bail(rc);
   *e->h_comm_err = 0;
-  if (hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_comm_err_dev), e->h_comm_err, 0) != hipSuccess) return bail(PBA_ERR_HIP);
   if ((rc = dev_alloc(e, &e->d_ticket_solve, (size_t)1))) return bail(rc);
   if (hipMemsetAsync(e->d_ticket_solve, 0, sizeof(unsigned int), e->stream) != hipSuccess) return bail(PBA_ERR_HIP);
   if (const char* sv = getenv("PBA_SOLVE")) e->solve_kind = atoi(sv);
   for (int k = 0; k < 2 * pba_engine::kEvPairs; ++k)
-    if (hipEventCreate(&e->ev[k]) != hipSuccess) return bail(PBA_ERR_HIP);
-  if (hipEventCreateWithFlags(&e->ev_xdep, hipEventDisableTiming) != hipSuccess) return bail(PBA_ERR_HIP);
+    if ((rc = handle_event(e, &e->ev[k]))) return bail(rc);
+  if ((rc = handle_event(e, &e->ev_xdep, hipEventDisableTiming))) return bail(rc);
   e->sample_waves = sample_waves_for_radius(cfg->radius);
-  if ((rc = ensure_state_stage(e, (size_t)6 * mf + 3 * 65536))) return bail(rc);   // grown on demand beyond 64k points
+  if ((rc = host_alloc(e, &e->h_state_stage, (size_t)6 * mf + 3 * 65536, &e->h_state_dev))) return bail(rc);   // grown on demand beyond 64k points
   // The first frame-sized host -> device DMA of a process costs ~8 ms (seen in the drop-in class: first
   // pba_set_frame_u8): paid here, from the engine's own pinned buffer
   if (hipMemcpyAsync(e->d_img_stage, e->h_img_stage, npix, hipMemcpyHostToDevice, e->stream) != hipSuccess) return bail(PBA_ERR_HIP);
@@ -869,45 +830,18 @@ int pba_create(const pba_config* cfg, pba_engine** out) {
 
 void pba_destroy(pba_engine* e) {
   if (!e) return;
-  (void)hipSetDevice(e->cfg.device);
   if (e->poisoned) {
     // the stream holds work that will never finish (pba_step / pba_solve timed out): waiting for it, freeing memory it
     // may still touch or destroying its stream would hang or fault; abort the communicator and leak the device side
+    (void)hipSetDevice(e->cfg.device);
+    e->mem.abandon();
     e->comm.shutdown(true);
     delete e;
     return;
   }
-  if (e->stream) (void)hipStreamSynchronize(e->stream);
+  handle_drain(e);
   e->comm.shutdown();
-  dev_free(&e->d_frames); dev_free(&e->d_img_stage); dev_free(&e->d_frames_mc);
-  for (int k = 0; k < 2; ++k) { dev_free(&e->d_xyz[k]); dev_free(&e->d_cams[k]); dev_free(&e->d_geom[k]); dev_free(&e->d_block_cost[k]); dev_free(&e->d_block_fail[k]); }
-  dev_free(&e->d_rays);
-  dev_free(&e->d_desc); dev_free(&e->d_w2); dev_free(&e->d_obs_point); dev_free(&e->d_obs_slot); dev_free(&e->d_pt_begin);
-  dev_free(&e->d_tile_info); dev_free(&e->d_lane_rec); dev_free(&e->d_rec[0]); dev_free(&e->d_rec[1]); dev_free(&e->d_sp); dev_free(&e->d_ptrec); dev_free(&e->d_sc);
-  dev_free(&e->d_delta_c); dev_free(&e->d_partial); dev_free(&e->d_red); dev_free(&e->d_packed); dev_free(&e->d_solve_tab); dev_free(&e->d_S);
-  dev_free(&e->d_rhs); dev_free(&e->d_bs_out); dev_free(&e->d_scal); dev_free(&e->d_xchg); dev_free(&e->d_ticket); dev_free(&e->d_ticket_solve); dev_free(&e->d_stamp);
-  if (e->h_scal) (void)hipHostFree(e->h_scal);
-  if (e->h_lm) (void)hipHostFree(e->h_lm);
-  if (e->h_comm_err) (void)hipHostFree(e->h_comm_err);
-  if (e->h_img_stage) (void)hipHostFree(e->h_img_stage);
-  if (e->h_state_stage) (void)hipHostFree(e->h_state_stage);
-  if (e->ev_img_stage) (void)hipEventDestroy(e->ev_img_stage);
-  if (e->ev_xdep) (void)hipEventDestroy(e->ev_xdep);
-  dev_free(&e->d_u8_work[0]); dev_free(&e->d_u8_work[1]);
-  dev_free(&e->d_fe_mask); dev_free(&e->d_fe_flag); dev_free(&e->d_fe_smap); dev_free(&e->d_fe_depth); dev_free(&e->d_fe_rows);
-  dev_free(&e->d_fe_cand); dev_free(&e->d_fe_io);
-  if (e->h_fe_io) (void)hipHostFree(e->h_fe_io);
-  if (e->h_log) (void)hipHostFree(e->h_log);
-  if (e->h_batch) (void)hipHostFree(e->h_batch);
-  dev_free(&e->d_batch);
-  dev_free(&e->d_lm);
-  dev_free(&e->d_log);
-  dev_free(&e->d_res_sync);
-  dev_free(&e->d_pose_partial); dev_free(&e->d_pose_sums);
-  dev_free(&e->d_pts_sys); dev_free(&e->d_pts_part); dev_free(&e->d_pts_V); dev_free(&e->d_pts_rhs);
-  dev_free(&e->d_wfac); dev_free(&e->d_wpt_part); dev_free(&e->d_went); dev_free(&e->d_wchunk); dev_free(&e->d_wpair_chunk); dev_free(&e->d_wsums);
-  for (int k = 0; k < 2 * pba_engine::kEvPairs; ++k) if (e->ev[k]) (void)hipEventDestroy(e->ev[k]);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
+  handle_close(e);
   delete e;
 }
 
@@ -915,8 +849,7 @@ int pba_set_frame_channels_f32(pba_engine* e, int slot, int32_t n_channels, cons
   if (!e || !channels || slot < 0 || slot >= e->cfg.max_frames) return PBA_ERR_INVALID;
   if (e->channels <= 1 || n_channels != e->channels)
     return fail(e, PBA_ERR_INVALID, "pba_set_frame_channels_f32: the engine was created for %d channel(s), got %d", e->channels, n_channels);
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   const size_t npix = (size_t)e->cfg.rows * e->cfg.cols;
   // the slot keeps the channel VALUES as they come ([C][rows*cols], the layout of the argument): one copy, no kernel; the
   // caller's buffer is only borrowed for the call
@@ -931,8 +864,7 @@ int pba_set_frame_channels_f32(pba_engine* e, int slot, int32_t n_channels, cons
 int pba_set_frame_u8(pba_engine* e, int slot, const uint8_t* image) {
   if (!e || !image || slot < 0 || slot >= e->cfg.max_frames) return PBA_ERR_INVALID;
   if (e->channels > 1) return fail(e, PBA_ERR_INVALID, "pba_set_frame_u8: the engine was created for %d channels (pba_set_frame_channels_f32)", e->channels);
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   const size_t npix = (size_t)e->cfg.rows * e->cfg.cols;
   // The caller's buffer is only borrowed for the call: it is copied into a pinned staging buffer here, and the upload +
   // packing run asynchronously behind the return (a pageable hipMemcpy plus a stream sync cost ~1.2 ms per frame).
@@ -954,19 +886,17 @@ int pba_set_frame_u8(pba_engine* e, int slot, const uint8_t* image) {
 int pba_get_frame_planes(pba_engine* e, int slot, float* I, float* Gx, float* Gy) {
   if (!e || slot < 0 || slot >= e->cfg.max_frames || !I || !Gx || !Gy) return PBA_ERR_INVALID;
   if (e->channels > 1) return fail(e, PBA_ERR_INVALID, "pba_get_frame_planes reads the single-channel planes");
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   const size_t npix = (size_t)e->cfg.rows * e->cfg.cols;
-  float* d = nullptr;
-  HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&d), 3 * npix * sizeof(float)));
+  DeviceTemp<float> tmp;
+  HIP_TRY(e, tmp.alloc(3 * npix));
+  float* d = tmp.p;
   hipLaunchKernelGGL(k_unpack_frame, dim3((npix + 255) / 256), dim3(256), 0, e->stream, e->d_frames + npix * slot, d,
                      d + npix, d + 2 * npix, (int)npix);
-  hipError_t r = hipMemcpyAsync(I, d, npix * sizeof(float), hipMemcpyDeviceToHost, e->stream);
-  if (r == hipSuccess) r = hipMemcpyAsync(Gx, d + npix, npix * sizeof(float), hipMemcpyDeviceToHost, e->stream);
-  if (r == hipSuccess) r = hipMemcpyAsync(Gy, d + 2 * npix, npix * sizeof(float), hipMemcpyDeviceToHost, e->stream);
-  if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-  (void)hipFree(d);
-  if (r != hipSuccess) return fail(e, PBA_ERR_HIP, "pba_get_frame_planes: %s", hipGetErrorString(r));
+  HIP_TRY(e, hipMemcpyAsync(I, d, npix * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(Gx, d + npix, npix * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(Gy, d + 2 * npix, npix * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
   return PBA_OK;
 }
 
@@ -974,19 +904,17 @@ int pba_get_frame_channel(pba_engine* e, int slot, int32_t channel, float* I, fl
   if (!e || slot < 0 || slot >= e->cfg.max_frames || !I || !Gx || !Gy) return PBA_ERR_INVALID;
   if (e->channels <= 1 || channel < 0 || channel >= e->channels)
     return fail(e, PBA_ERR_INVALID, "pba_get_frame_channel: channel %d of an engine with %d channel(s)", channel, e->channels);
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   const size_t npix = (size_t)e->cfg.rows * e->cfg.cols;
-  float* d = nullptr;
-  HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&d), 3 * npix * sizeof(float)));
+  DeviceTemp<float> tmp;
+  HIP_TRY(e, tmp.alloc(3 * npix));
+  float* d = tmp.p;
   hipLaunchKernelGGL(k_unpack_channel, dim3((e->cfg.cols + 255) / 256, e->cfg.rows), dim3(256), 0, e->stream,
                      (const float*)e->d_frames_mc + ((size_t)slot * e->channels + channel) * npix, e->cfg.rows, e->cfg.cols, d, d + npix, d + 2 * npix);
-  hipError_t r = hipMemcpyAsync(I, d, npix * sizeof(float), hipMemcpyDeviceToHost, e->stream);
-  if (r == hipSuccess) r = hipMemcpyAsync(Gx, d + npix, npix * sizeof(float), hipMemcpyDeviceToHost, e->stream);
-  if (r == hipSuccess) r = hipMemcpyAsync(Gy, d + 2 * npix, npix * sizeof(float), hipMemcpyDeviceToHost, e->stream);
-  if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-  (void)hipFree(d);
-  if (r != hipSuccess) return fail(e, PBA_ERR_HIP, "pba_get_frame_channel: %s", hipGetErrorString(r));
+  HIP_TRY(e, hipMemcpyAsync(I, d, npix * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(Gx, d + npix, npix * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(Gy, d + 2 * npix, npix * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
   return PBA_OK;
 }
 
@@ -994,8 +922,7 @@ int pba_get_frame_channels_f32(pba_engine* e, int slot, float* channels) {
   if (!e || slot < 0 || slot >= e->cfg.max_frames || !channels) return PBA_ERR_INVALID;
   if (e->channels <= 1) return fail(e, PBA_ERR_INVALID, "pba_get_frame_channels_f32: single-channel engine");
   if (!e->frame_set[slot]) return fail(e, PBA_ERR_STATE, "pba_get_frame_channels_f32: slot %d holds no frame", slot);
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   const size_t n = (size_t)e->channels * e->cfg.rows * e->cfg.cols;
   HIP_TRY(e, hipMemcpyAsync(channels, e->d_frames_mc + (size_t)slot * n, n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));
@@ -1005,27 +932,23 @@ int pba_get_frame_channels_f32(pba_engine* e, int slot, float* channels) {
 int pba_sample_frame(pba_engine* e, int slot, int32_t channel, int32_t n, const float* y, const float* x, float* out3) {
   if (!e || slot < 0 || slot >= e->cfg.max_frames || n <= 0 || !y || !x || !out3 || channel < 0 || channel >= e->channels) return PBA_ERR_INVALID;
   if (!e->frame_set[slot]) return fail(e, PBA_ERR_STATE, "pba_sample_frame: slot %d holds no frame", slot);
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   const size_t npix = (size_t)e->cfg.rows * e->cfg.cols;
-  float* d = nullptr;
-  HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&d), (size_t)5 * n * sizeof(float)));
-  hipError_t r = hipMemcpyAsync(d, y, (size_t)n * sizeof(float), hipMemcpyHostToDevice, e->stream);
-  if (r == hipSuccess) r = hipMemcpyAsync(d + n, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, e->stream);
-  if (r == hipSuccess) {
-    if (e->channels > 1)
-      hipLaunchKernelGGL(k_sample_probe_mc, dim3((n + 255) / 256), dim3(256), 0, e->stream,
-                         (const float*)e->d_frames_mc + ((size_t)slot * e->channels + channel) * npix, e->cfg.rows, e->cfg.cols, n,
-                         (const float*)d, (const float*)(d + n), d + 2 * (size_t)n);
-    else
-      hipLaunchKernelGGL(k_sample_probe, dim3((n + 255) / 256), dim3(256), 0, e->stream, (const uint32_t*)(e->d_frames + npix * slot),
-                         e->cfg.rows, e->cfg.cols, n, (const float*)d, (const float*)(d + n), d + 2 * (size_t)n);
-    r = hipGetLastError();
-  }
-  if (r == hipSuccess) r = hipMemcpyAsync(out3, d + 2 * (size_t)n, (size_t)3 * n * sizeof(float), hipMemcpyDeviceToHost, e->stream);
-  if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-  (void)hipFree(d);
-  if (r != hipSuccess) return fail(e, PBA_ERR_HIP, "pba_sample_frame: %s", hipGetErrorString(r));
+  DeviceTemp<float> tmp;
+  HIP_TRY(e, tmp.alloc((size_t)5 * n));
+  float* d = tmp.p;
+  HIP_TRY(e, hipMemcpyAsync(d, y, (size_t)n * sizeof(float), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(d + n, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, e->stream));
+  if (e->channels > 1)
+    hipLaunchKernelGGL(k_sample_probe_mc, dim3((n + 255) / 256), dim3(256), 0, e->stream,
+                       (const float*)e->d_frames_mc + ((size_t)slot * e->channels + channel) * npix, e->cfg.rows, e->cfg.cols, n,
+                       (const float*)d, (const float*)(d + n), d + 2 * (size_t)n);
+  else
+    hipLaunchKernelGGL(k_sample_probe, dim3((n + 255) / 256), dim3(256), 0, e->stream, (const uint32_t*)(e->d_frames + npix * slot),
+                       e->cfg.rows, e->cfg.cols, n, (const float*)d, (const float*)(d + n), d + 2 * (size_t)n);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipMemcpyAsync(out3, d + 2 * (size_t)n, (size_t)3 * n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
   return PBA_OK;
 }
 
@@ -1049,8 +972,7 @@ int pba_set_frame_descriptor_u8(pba_engine* e, int slot, const uint8_t* image, i
   if (!want) return fail(e, PBA_ERR_INVALID, "pba_set_frame_descriptor_u8: unknown descriptor %d", descriptor);
   if (e->channels != want)
     return fail(e, PBA_ERR_INVALID, "pba_set_frame_descriptor_u8: descriptor %d has %d channels, the engine was created for %d", descriptor, want, e->channels);
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   const int rows = e->cfg.rows, cols = e->cfg.cols;
   const size_t npix = (size_t)rows * cols;
   int rc;
@@ -1122,14 +1044,7 @@ int pba_set_frame_pyr_down(pba_engine* e, int slot, pba_engine* finer, int finer
 }
 
 // ---- device front-end ---------------------------------------------------------------------------------------------------
-static int fe_stage(pba_engine* e, size_t bytes) {      // pinned staging buffer of the front-end calls, grow-only
-  if (e->h_fe_cap >= bytes) return PBA_OK;
-  if (e->h_fe_io) { (void)hipHostFree(e->h_fe_io); e->h_fe_io = nullptr; e->h_fe_cap = 0; }
-  const size_t want = bytes + bytes / 4 + 4096;
-  HIP_TRY(e, hipHostMalloc(reinterpret_cast<void**>(&e->h_fe_io), want, hipHostMallocDefault));
-  e->h_fe_cap = want;
-  return PBA_OK;
-}
+static int fe_stage(pba_engine* e, size_t bytes) { return host_alloc(e, &e->h_fe_io, bytes); }      // pinned staging buffer of the front-end calls
 
 int pba_frontend_visibility(pba_engine* e, int32_t n, const double* uv, const int32_t* rc, const float* patches26, double min_score,
                             int32_t mask_radius, uint8_t* hit) {
@@ -1198,8 +1113,7 @@ int pba_frontend_candidates(pba_engine* e, int32_t slot, const float* depth, dou
   if (nms_radius > border) return fail(e, PBA_ERR_INVALID, "pba_frontend_candidates: nms radius %d reaches over the border %d", nms_radius, border);
   if (2 * border >= e->cfg.rows || 2 * border >= e->cfg.cols)
     return fail(e, PBA_ERR_INVALID, "pba_frontend_candidates: border %d leaves no interior in a %d x %d image", border, e->cfg.rows, e->cfg.cols);
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   const int rows = e->cfg.rows, cols = e->cfg.cols;
   const size_t npix = (size_t)rows * cols;
   int rcode;
@@ -1238,8 +1152,7 @@ int pba_frontend_get_candidates(pba_engine* e, pba_candidate* out, int32_t n) {
   if (!e || n < 0 || (n > 0 && !out)) return PBA_ERR_INVALID;
   if (n > e->fe_n_cand) return fail(e, PBA_ERR_STATE, "pba_frontend_get_candidates: %d requested, the last scan found %d", n, e->fe_n_cand);
   if (n == 0) return PBA_OK;
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   { const int rcode = fe_stage(e, (size_t)n * sizeof(pba_candidate)); if (rcode) return rcode; }
   HIP_TRY(e, hipMemcpyAsync(e->h_fe_io, e->d_fe_cand, (size_t)n * sizeof(pba_candidate), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));
@@ -1251,8 +1164,7 @@ int pba_frontend_descriptors(pba_engine* e, int32_t slot, int32_t n, const int32
   if (!e || n < 0 || slot < 0 || slot >= e->cfg.max_frames || (n > 0 && (!xy || !desc))) return PBA_ERR_INVALID;
   if (!e->frame_set[slot]) return fail(e, PBA_ERR_STATE, "pba_frontend_descriptors: slot %d holds no frame", slot);
   if (n == 0) return PBA_OK;
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   const int rows = e->cfg.rows, cols = e->cfg.cols, R = e->cfg.radius, P = (2 * R + 1) * (2 * R + 1);
   const size_t npix = (size_t)rows * cols;
   const size_t b_xy = (size_t)n * 8, b_out = (size_t)n * e->channels * P * sizeof(float);
@@ -1276,8 +1188,7 @@ int pba_frontend_descriptors(pba_engine* e, int32_t slot, int32_t n, const int32
 int pba_set_problem(pba_engine* e, int32_t n_points, const double* xyz, const double* desc, int32_t n_obs,
                     const int32_t* obs_point, const int32_t* obs_slot, const double* weights) {
   if (!e || n_points <= 0 || n_obs <= 0 || !xyz || !desc || !obs_point || !obs_slot || !weights) return PBA_ERR_INVALID;
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   const int P = (2 * e->cfg.radius + 1) * (2 * e->cfg.radius + 1);     // pixels of one patch (weights)
   const int PD = P * e->channels;                                       // descriptor entries per point
   // validate + CSR + tiles (whole points per tile of <= kTile observations)
@@ -1383,8 +1294,7 @@ int pba_set_problem(pba_engine* e, int32_t n_points, const double* xyz, const do
 
 int pba_set_cameras(pba_engine* e, const double* cams6, int32_t n_frames, int32_t fixed_slot) {
   if (!e || !cams6 || n_frames < 2 || n_frames > e->cfg.max_frames || fixed_slot >= n_frames) return PBA_ERR_INVALID;
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   {
     // the window shape picks the path: up to kWideMinFree - 1 free cameras the narrow kernels, beyond them the wide chain
     const int nf = n_frames - (fixed_slot >= 0 ? 1 : 0);
@@ -1444,13 +1354,12 @@ int pba_set_cameras(pba_engine* e, const double* cams6, int32_t n_frames, int32_
 }
 
 static int fetch_state(pba_engine* e, double* cams6, double* xyz) {
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   // through the engine's host-mapped pinned buffer, written by a kernel: the runtime's copy call blocks for 8 ms the
   // first time a process moves a few hundred KB device -> host (seen in the drop-in class, pinned or pageable
   // destination alike); a kernel that stores over PCIe plus a host copy is ~50 us every time
   const size_t nc = (size_t)6 * e->n_frames, nx = (size_t)3 * e->n_points;
-  { const int rc = ensure_state_stage(e, nc + nx); if (rc) return rc; }
+  { const int rc = host_alloc(e, &e->h_state_stage, nc + nx, &e->h_state_dev); if (rc) return rc; }
   if (cams6) k_to_host<<<dim3(1), dim3(256), 0, e->stream>>>(e->d_cams[e->cur], e->h_state_dev, nc);
   if (xyz) k_to_host<<<dim3((unsigned)std::min<size_t>((nx + 1023) / 1024, 256)), dim3(256), 0, e->stream>>>(e->d_xyz[e->cur], e->h_state_dev + nc, nx);
   HIP_TRY(e, hipGetLastError());
@@ -1472,8 +1381,7 @@ int pba_set_inverse_depth(pba_engine* e, const double* rays6, const double* rho)
   if (!e->have_problem) return fail(e, PBA_ERR_STATE, "call order violated: pba_set_inverse_depth before pba_set_problem");
   if (e->have_cams && e->wide)
     return fail(e, PBA_ERR_INVALID, "pba_set_inverse_depth: the inverse-depth mode is not built for wide windows (%d free cameras)", e->n_free);
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   const int n = e->n_points;
   std::vector<double> prm((size_t)3 * n, 0.0);
   for (int i = 0; i < n; ++i) {
@@ -1563,8 +1471,7 @@ static int points_sync_cameras(pba_engine* e) {
 int pba_get_points_world(pba_engine* e, double* xyz) {
   if (!e || !xyz) return PBA_ERR_INVALID;
   if (!e->have_problem) return fail(e, PBA_ERR_STATE, "call order violated: pba_get_points_world before pba_set_problem");
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   { const int rc = fetch_state(e, nullptr, xyz); if (rc) return rc; }
   if (e->inverse_depth) {
     for (int i = 0; i < e->n_points; ++i) {
@@ -1579,8 +1486,7 @@ int pba_get_points_world(pba_engine* e, double* xyz) {
 int pba_linearize(pba_engine* e, double* cost) {
   if (!e) return PBA_ERR_INVALID;
   { const int rc0 = check_ready(e, "pba_linearize"); if (rc0) return rc0; }
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   if (e->points_const) { const int rcp = pose_sync_points(e); if (rcp) return rcp; }
   if (e->cams_const) { const int rcp = points_sync_cameras(e); if (rcp) return rcp; }
   if (!e->lin_valid[e->cur]) {
@@ -1802,8 +1708,7 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
   if (!e || !o || !out || !(radius > 0.0)) return PBA_ERR_INVALID;
   e->last_driver = 3;
   if (!e->have_lin) return fail(e, PBA_ERR_STATE, "call order violated: pba_step before pba_linearize");
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   if (e->points_const) return pose_step(e, radius, init_scale, o, out, scal, grad_only);
   if (e->cams_const) return points_step(e, radius, init_scale, o, out, scal, grad_only);
   const int cur = e->cur, cand = 1 - e->cur;
@@ -1812,7 +1717,7 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
 
   SchurParams sc = schur_params(e, cur, init_scale, o, radius);
   if (e->dbg_left > 0 && !e->wide) {
-    if (!e->d_dbg) { (void)hipMalloc(reinterpret_cast<void**>(&e->d_dbg), sizeof(unsigned long long) * 8 * (1024 + 4096)); }
+    { const int rcd = dev_alloc(e, &e->d_dbg, pba_engine::kDbgWords); if (rcd) return rcd; }
     sc.dbg = e->d_dbg;
   }
   if (e->wide) {
@@ -1896,8 +1801,7 @@ int pba_get_point_system(pba_engine* e, double* V9, double* rhs3) {
   if (!(e->cfg.flags & 1)) return fail(e, PBA_ERR_STATE, "call order violated: pba_get_point_system needs pba_config.flags bit 0 (keep reduced system)");
   if (!e->cams_const || !e->pts_dbg_valid)
     return fail(e, PBA_ERR_STATE, "call order violated: pba_get_point_system needs a pba_step in the cameras-constant mode (pba_set_cameras_constant)");
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   if (V9) HIP_TRY(e, hipMemcpyAsync(V9, e->d_pts_V, sizeof(double) * 9 * e->n_points, hipMemcpyDeviceToHost, e->stream));
   if (rhs3) HIP_TRY(e, hipMemcpyAsync(rhs3, e->d_pts_rhs, sizeof(double) * 3 * e->n_points, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));
@@ -1908,8 +1812,7 @@ int pba_get_reduced_system(pba_engine* e, double* S, double* rhs, int32_t* n_out
   if (!e || !n_out) return PBA_ERR_INVALID;
   if (!(e->cfg.flags & 1)) return fail(e, PBA_ERR_STATE, "call order violated: pba_get_reduced_system needs pba_config.flags bit 0 (keep reduced system)");
   if (e->cams_const) return fail(e, PBA_ERR_STATE, "pba_get_reduced_system: the cameras-constant mode (pba_set_cameras_constant) has no reduced camera system; see pba_get_point_system");
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   const int n = 6 * e->n_free;
   *n_out = n;
   if (S) HIP_TRY(e, hipMemcpyAsync(S, e->d_S, sizeof(double) * n * n, hipMemcpyDeviceToHost, e->stream));
@@ -1921,8 +1824,7 @@ int pba_get_reduced_system(pba_engine* e, double* S, double* rhs, int32_t* n_out
 int pba_get_obs_records(pba_engine* e, double* rec6) {
   if (!e || !rec6) return PBA_ERR_INVALID;
   if (!e->have_problem) return fail(e, PBA_ERR_STATE, "no problem");
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   std::vector<double> tmp((size_t)6 * e->rec_stride);
   HIP_TRY(e, hipMemcpyAsync(tmp.data(), e->d_rec[e->cur], sizeof(double) * tmp.size(), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));
@@ -1941,8 +1843,7 @@ int pba_comm_init_rccl(pba_engine* e, const void* id128, int32_t rank, int32_t w
     return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for the points-constant mode (pba_set_points_constant)");
   if (world > 1 && e->cams_const)
     return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for the cameras-constant mode (pba_set_cameras_constant)");
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   if (e->comm.init_rccl(id128, rank, world)) return fail(e, PBA_ERR_COMM, "%s", e->comm.err.c_str());
   return PBA_OK;
 }
@@ -1955,8 +1856,7 @@ int pba_comm_init_callback(pba_engine* e, pba_allreduce_fn fn, void* ctx, int32_
     return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for the points-constant mode (pba_set_points_constant)");
   if (world > 1 && e->cams_const)
     return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for the cameras-constant mode (pba_set_cameras_constant)");
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   if (e->comm.init_callback(fn, ctx, rank, world)) return fail(e, PBA_ERR_COMM, "%s", e->comm.err.c_str());
   return PBA_OK;
 }
@@ -1964,8 +1864,7 @@ int pba_comm_init_callback(pba_engine* e, pba_allreduce_fn fn, void* ctx, int32_
 int pba_comm_enable_peer_exchange(pba_engine* e) {
   if (!e) return PBA_ERR_INVALID;
   if (e->comm.kind == 0) return fail(e, PBA_ERR_STATE, "call order violated: pba_comm_enable_peer_exchange before pba_comm_init_*");
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   if (e->comm.enable_peer()) e->err = e->comm.err;      // not an error: the base transport keeps serving (pba_comm_transport tells)
   return PBA_OK;
@@ -1989,8 +1888,7 @@ int pba_get_counters(pba_engine* e, pba_counters* c) {
   if (e->stamps && e->d_stamp && e->last_driver == 1) {
     // resident solve: phase stamps of the serial workgroup.  The three counters keep their meaning as SHARES OF THE ITERATION: elimination
     // (k_schur's work) | reduction of the partials + reduced solve (k_reduce_solve's) | back-substitution + sampling + decision (k_sample's)
-    PBA_NOT_POISONED(e);
-    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    PBA_ENTER(e);
     const int n_rec = std::min(std::max(e->stamp_iter, 0) + 2, (int)kStampMaxIters);
     std::vector<unsigned long long> st((size_t)n_rec * kResStampRecord);
     HIP_TRY(e, hipMemcpyAsync(st.data(), e->d_stamp, sizeof(unsigned long long) * st.size(), hipMemcpyDeviceToHost, e->stream));
@@ -2010,8 +1908,7 @@ int pba_get_counters(pba_engine* e, pba_counters* c) {
     e->ctr.solve_ms = 1e-5 * d_solve; e->ctr.solve_launches = n;
   } else if (e->stamps && e->d_stamp) {
     // device time stamps of the LAST asynchronous solve (100 MHz ticks): intervals between consecutive kernel ends
-    PBA_NOT_POISONED(e);
-    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    PBA_ENTER(e);
     const int n_rec = std::min(e->stamp_iter, (int)kStampMaxIters) + 1;
     std::vector<unsigned long long> st((size_t)n_rec * kStampRecord);
     HIP_TRY(e, hipMemcpyAsync(st.data(), e->d_stamp, sizeof(unsigned long long) * st.size(), hipMemcpyDeviceToHost, e->stream));
@@ -2047,8 +1944,7 @@ int pba_reset_counters(pba_engine* e) {
 
 int pba_set_profiling(pba_engine* e, int32_t mode) {
   if (!e || mode < 0 || mode > 2) return PBA_ERR_INVALID;
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   const int64_t no = e->ctr.n_obs, np = e->ctr.n_points;
   e->ctr = pba_counters{};
   e->ctr.n_obs = no; e->ctr.n_points = np;
@@ -2117,8 +2013,7 @@ int pba_internal_final_flushes(const pba_engine* e) {
 
 int pba_internal_async_begin(pba_engine* e, const pba_solver_options* o) {
   { const int rc0 = check_ready(e, "pba_solve"); if (rc0) return rc0; }
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   const LmState st = lm_initial_state(o, e->cur);
   *e->h_lm = st;
   // The device copy of the initial state is made by the first kernel of the solve (workgroup 0 of the kind-0 sampling pass reads the
@@ -2352,8 +2247,7 @@ int pba_internal_resident_capable(pba_engine* e, const pba_solver_options* o) {
 
 int pba_internal_resident_launch(pba_engine* e, const pba_solver_options* o, unsigned long long* seq_out) {
   { const int rc0 = check_ready(e, "pba_solve"); if (rc0) return rc0; }
-  PBA_NOT_POISONED(e);
-  HIP_TRY(e, hipSetDevice(e->cfg.device));
+  PBA_ENTER(e);
   *e->h_lm = lm_initial_state(o, e->cur);
   __atomic_thread_fence(__ATOMIC_RELEASE);
   ResidentParams P{};
@@ -2396,7 +2290,7 @@ int pba_internal_resident_launch(pba_engine* e, const pba_solver_options* o, uns
     HIP_TRY(e, hipMemsetAsync(e->d_stamp, 0, sizeof(unsigned long long) * kResStampRecord * (o->max_num_iterations + 2), e->stream));
     P.stamp = e->d_stamp;
     if (atoi(getenv("PBA_RES_TRACE")) >= 2) {
-      if (!e->d_dbg) { (void)hipMalloc(reinterpret_cast<void**>(&e->d_dbg), sizeof(unsigned long long) * 8 * (1024 + 4096)); }
+      { const int rcd = dev_alloc(e, &e->d_dbg, pba_engine::kDbgWords); if (rcd) return rcd; }
       P.schur_dbg = e->d_dbg;
     }
   }
@@ -2538,14 +2432,8 @@ int pba_internal_batch_begin(pba_engine* const* es, int32_t n, const pba_solver_
     HIP_TRY(e0, hipStreamWaitEvent(bs, es[i]->ev_xdep, 0));
   }
   for (int i = 0; i < n; ++i) { es[i]->stream_own = es[i]->stream; es[i]->stream = bs; }
-  if (e0->batch_cap < n) {
-    if (e0->h_batch) { (void)hipHostFree(e0->h_batch); e0->h_batch = nullptr; }
-    e0->batch_cap = 0;
-    HIP_TRY(e0, hipHostMalloc(reinterpret_cast<void**>(&e0->h_batch), sizeof(BatchWindow) * PBA_MAX_BATCH, hipHostMallocDefault));
-    const int rc = dev_alloc(e0, &e0->d_batch, (size_t)PBA_MAX_BATCH);
-    if (rc) return rc;
-    e0->batch_cap = PBA_MAX_BATCH;
-  }
+  if (const int rc = host_alloc(e0, &e0->h_batch, (size_t)PBA_MAX_BATCH)) return rc;      // the window table and its staging: on the first batch
+  if (const int rc = dev_alloc(e0, &e0->d_batch, (size_t)PBA_MAX_BATCH)) return rc;
   for (int i = 0; i < n; ++i) {
     pba_engine* e = es[i];
     const int rc = pba_internal_async_begin(e, &o[i]);

@@ -25,13 +25,11 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
 
 #include "../../include/pba_sgm.h"
+#include "pba_handle.h"
 
 namespace {
 
@@ -345,26 +343,13 @@ __global__ __launch_bounds__(256) void k_sgm_lr_depth(const uint16_t* __restrict
   if (depth) depth[p] = d > 0.01f ? __fmul_rn(bf, __fdiv_rn(1.0f, d)) : -0.1f;
 }
 
-thread_local std::string g_sgm_create_err;
-
-int create_fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_sgm_create_err = buf;
-  return code;
-}
-
 }  // namespace
 
-struct pba_sgm {
-  int rows = 0, cols = 0, device = 0;
+struct pba_sgm : pba::Handle {      // (device, stream, err, mem, events)
+  int rows = 0, cols = 0;
   pba_sgm_params p{};
   int cap = 15;
   HammingTable ht{};
-  hipStream_t stream = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // upload start, kernels start, kernels end, copy-back end
   uint8_t* d_img = nullptr;       // left, right
   uint8_t* d_sobel = nullptr;     // left, right
@@ -385,26 +370,12 @@ struct pba_sgm {
   float* h_disparity = nullptr;
   float* h_depth = nullptr;
   bool computed = false;
-  std::string err;
 };
 
 namespace {
 
-int fail(pba_sgm* s, int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  s->err = buf;
-  return code;
-}
-
-#define SGM_HIP_TRY(s, call)                                                                     \
-  do {                                                                                           \
-    hipError_t _r = (call);                                                                      \
-    if (_r != hipSuccess) return fail((s), PBA_ERR_HIP, "%s: %s", #call, hipGetErrorString(_r)); \
-  } while (0)
+using pba::MemKind;      // (fail and create_bail are found through the handle argument)
+constexpr auto create_fail = pba::create_fail<pba_sgm>;
 
 int effective_cap(int v) { return std::min(std::max(v, 15), 127) | 1; }
 
@@ -471,23 +442,9 @@ int pba_sgm_validate_params(int32_t rows, int32_t cols, const pba_sgm_params* p)
   return validate(rows, cols, p);
 }
 
-const char* pba_sgm_last_error(const pba_sgm* s) { return s ? s->err.c_str() : g_sgm_create_err.c_str(); }
+const char* pba_sgm_last_error(const pba_sgm* s) { return s ? s->err.c_str() : pba::create_error<pba_sgm>().c_str(); }
 
-void pba_sgm_destroy(pba_sgm* s) {
-  if (!s) return;
-  if (s->stream) (void)hipStreamSynchronize(s->stream);
-  for (hipEvent_t& e : s->ev)
-    if (e) (void)hipEventDestroy(e);
-  void* dev[] = {s->d_img, s->d_sobel, s->d_census, s->d_agg, s->d_cost, s->d_sum, s->d_raw, s->d_filtered,
-                 s->d_parent, s->d_root, s->d_size, s->d_disp, s->d_disparity, s->d_depth};
-  for (void* q : dev)
-    if (q) (void)hipFree(q);
-  void* host[] = {s->h_img, s->h_disp, s->h_disparity, s->h_depth};
-  for (void* q : host)
-    if (q) (void)hipHostFree(q);
-  if (s->stream) (void)hipStreamDestroy(s->stream);
-  delete s;
-}
+void pba_sgm_destroy(pba_sgm* s) { pba::handle_destroy(s); }
 
 int pba_sgm_create(int32_t rows, int32_t cols, const pba_sgm_params* p, int32_t device, pba_sgm** out) {
   if (!out) return create_fail(PBA_ERR_INVALID, "out is NULL");
@@ -496,42 +453,29 @@ int pba_sgm_create(int32_t rows, int32_t cols, const pba_sgm_params* p, int32_t 
   if (rows == 0 && cols == 0) return create_fail(PBA_ERR_INVALID, "image size 0 x 0");
   int rc = validate(rows, cols, p);
   if (rc) return rc;
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || device < 0 || device >= n_dev) {
-    (void)hipGetLastError();
+  if (!pba::device_exists(device))
     return create_fail(PBA_ERR_NO_DEVICE, "no HIP device %d (the semi-global matcher has no CPU fallback)", device);
-  }
   pba_sgm* s = new pba_sgm();
   s->rows = rows;
   s->cols = cols;
-  s->device = device;
   s->p = *p;
   s->cap = effective_cap(p->sobel_cap_value);
   for (int h = 0; h < 26; ++h) s->ht.v[h] = (uint8_t)(int)(h * p->census_weight_factor);
-  auto bail = [&](int code) {
-    g_sgm_create_err = s->err;
-    pba_sgm_destroy(s);
-    return code;
-  };
   const size_t npix = (size_t)rows * cols, nvol = npix * p->number_of_disparities;
-  if (hipSetDevice(device) != hipSuccess) return bail(fail(s, PBA_ERR_HIP, "hipSetDevice(%d) failed", device));
-  if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(s, PBA_ERR_HIP, "hipStreamCreate failed"));
+  if ((rc = pba::handle_open(s, device))) return create_bail(s, rc, pba_sgm_destroy);
   for (hipEvent_t& e : s->ev)
-    if (hipEventCreate(&e) != hipSuccess) return bail(fail(s, PBA_ERR_HIP, "hipEventCreate failed"));
-  auto dmalloc = [](auto** q, size_t bytes) { return hipMalloc(reinterpret_cast<void**>(q), bytes) == hipSuccess; };
-  if (!dmalloc(&s->d_img, 2 * npix) || !dmalloc(&s->d_sobel, 2 * npix) || !dmalloc(&s->d_census, 2 * npix * sizeof(int32_t)) ||
-      !dmalloc(&s->d_agg, nvol * sizeof(uint16_t)) || !dmalloc(&s->d_cost, nvol * sizeof(uint16_t)) ||
-      !dmalloc(&s->d_sum, nvol * sizeof(int16_t)) || !dmalloc(&s->d_raw, 2 * npix * sizeof(uint16_t)) ||
-      !dmalloc(&s->d_filtered, 2 * npix * sizeof(uint16_t)) || !dmalloc(&s->d_parent, 2 * npix * sizeof(int)) ||
-      !dmalloc(&s->d_root, 2 * npix * sizeof(int)) || !dmalloc(&s->d_size, 2 * npix * sizeof(int)) ||
-      !dmalloc(&s->d_disp, npix * sizeof(uint16_t)) || !dmalloc(&s->d_disparity, npix * sizeof(float)) ||
-      !dmalloc(&s->d_depth, npix * sizeof(float)))
-    return bail(fail(s, PBA_ERR_HIP, "device allocation for %zu pixels x %d disparities failed", npix, p->number_of_disparities));
-  if (hipHostMalloc(reinterpret_cast<void**>(&s->h_img), 2 * npix, hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void**>(&s->h_disp), npix * sizeof(uint16_t), hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void**>(&s->h_disparity), npix * sizeof(float), hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void**>(&s->h_depth), npix * sizeof(float), hipHostMallocDefault) != hipSuccess)
-    return bail(fail(s, PBA_ERR_HIP, "pinned host allocation of %zu pixels failed", npix));
+    if ((rc = pba::handle_event(s, &e))) return create_bail(s, rc, pba_sgm_destroy);
+  const MemKind dev = MemKind::device, pin = MemKind::pinned;
+  if (s->mem.reserve(&s->d_img, dev, 2 * npix) || s->mem.reserve(&s->d_sobel, dev, 2 * npix) || s->mem.reserve(&s->d_census, dev, 2 * npix) ||
+      s->mem.reserve(&s->d_agg, dev, nvol) || s->mem.reserve(&s->d_cost, dev, nvol) || s->mem.reserve(&s->d_sum, dev, nvol) ||
+      s->mem.reserve(&s->d_raw, dev, 2 * npix) || s->mem.reserve(&s->d_filtered, dev, 2 * npix) || s->mem.reserve(&s->d_parent, dev, 2 * npix) ||
+      s->mem.reserve(&s->d_root, dev, 2 * npix) || s->mem.reserve(&s->d_size, dev, 2 * npix) || s->mem.reserve(&s->d_disp, dev, npix) ||
+      s->mem.reserve(&s->d_disparity, dev, npix) || s->mem.reserve(&s->d_depth, dev, npix))
+    return create_bail(s, fail(s, PBA_ERR_HIP, "device allocation for %zu pixels x %d disparities failed", npix, p->number_of_disparities),
+                       pba_sgm_destroy);
+  if (s->mem.reserve(&s->h_img, pin, 2 * npix) || s->mem.reserve(&s->h_disp, pin, npix) || s->mem.reserve(&s->h_disparity, pin, npix) ||
+      s->mem.reserve(&s->h_depth, pin, npix))
+    return create_bail(s, fail(s, PBA_ERR_HIP, "pinned host allocation of %zu pixels failed", npix), pba_sgm_destroy);
   *out = s;
   return PBA_OK;
 }
@@ -540,28 +484,28 @@ int pba_sgm_compute(pba_sgm* s, const uint8_t* left, const uint8_t* right, float
                     float* depth) {
   if (!s) return PBA_ERR_INVALID;
   if (!left || !right) return fail(s, PBA_ERR_INVALID, "pba_sgm_compute: left and right must not be NULL");
-  SGM_HIP_TRY(s, hipSetDevice(s->device));
+  PBA_HIP_TRY(s, hipSetDevice(s->device));
   const int H = s->rows, W = s->cols, D = s->p.number_of_disparities, r = s->p.window_radius;
   const size_t npix = (size_t)H * W;
   const size_t row = (size_t)W * D;
   hipStream_t st = s->stream;
   std::memcpy(s->h_img, left, npix);
   std::memcpy(s->h_img + npix, right, npix);
-  SGM_HIP_TRY(s, hipEventRecord(s->ev[0], st));
-  SGM_HIP_TRY(s, hipMemcpyAsync(s->d_img, s->h_img, 2 * npix, hipMemcpyHostToDevice, st));
-  SGM_HIP_TRY(s, hipEventRecord(s->ev[1], st));
+  PBA_HIP_TRY(s, hipEventRecord(s->ev[0], st));
+  PBA_HIP_TRY(s, hipMemcpyAsync(s->d_img, s->h_img, 2 * npix, hipMemcpyHostToDevice, st));
+  PBA_HIP_TRY(s, hipEventRecord(s->ev[1], st));
   hipLaunchKernelGGL(k_sgm_prefilter, dim3((W + 255) / 256, H, 2), dim3(256), 0, st, s->d_img, s->d_sobel, s->d_census, H, W, s->cap,
                      s->p.census_radius);
   hipLaunchKernelGGL(k_sgm_rowagg, grid1(row, H), dim3(256), 0, st, s->d_sobel, s->d_census, s->d_agg, H, W, D, r, s->ht);
   hipLaunchKernelGGL(k_sgm_cost, grid1(row), dim3(256), 0, st, s->d_agg, s->d_cost, H, W, D, r);
-  SGM_HIP_TRY(s, hipGetLastError());
+  PBA_HIP_TRY(s, hipGetLastError());
   int16_t* s_right = reinterpret_cast<int16_t*>(s->d_agg);
   const size_t lds = 2 * (size_t)(D + 2) * sizeof(int16_t);
   for (int pass = 0; pass < 2; ++pass)
     for (int column = 0; column < 2; ++column)
       hipLaunchKernelGGL(k_sgm_path, dim3(column ? W : H, 2), dim3(kWave), lds, st, s->d_cost, s->d_sum, s_right, H, W, D,
                          s->p.smoothness_penalty_small, s->p.smoothness_penalty_large, column, pass, (pass == 0 && column == 0) ? 1 : 0);
-  SGM_HIP_TRY(s, hipGetLastError());
+  PBA_HIP_TRY(s, hipGetLastError());
   hipLaunchKernelGGL(k_sgm_wta, grid1(npix, 2), dim3(256), 0, st, s->d_sum, s_right, s->d_raw, (int)npix, D, s->p.disparity_factor);
   hipLaunchKernelGGL(k_ccl_init, grid1(npix, 2), dim3(256), 0, st, s->d_parent, s->d_size, (int)npix);
   hipLaunchKernelGGL(k_ccl_merge, grid1(npix, 2), dim3(256), 0, st, s->d_raw, s->d_parent, H, W, (int)(2 * s->p.disparity_factor));
@@ -570,13 +514,13 @@ int pba_sgm_compute(pba_sgm* s, const uint8_t* left, const uint8_t* right, float
   hipLaunchKernelGGL(k_sgm_lr_depth, grid1(npix), dim3(256), 0, st, s->d_filtered, H, W, s->p.disparity_factor,
                      s->p.consistency_threshold, bf, disp_scaled ? s->d_disp : nullptr, disparity ? s->d_disparity : nullptr,
                      depth ? s->d_depth : nullptr);
-  SGM_HIP_TRY(s, hipGetLastError());
-  SGM_HIP_TRY(s, hipEventRecord(s->ev[2], st));
-  if (disp_scaled) SGM_HIP_TRY(s, hipMemcpyAsync(s->h_disp, s->d_disp, npix * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
-  if (disparity) SGM_HIP_TRY(s, hipMemcpyAsync(s->h_disparity, s->d_disparity, npix * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (depth) SGM_HIP_TRY(s, hipMemcpyAsync(s->h_depth, s->d_depth, npix * sizeof(float), hipMemcpyDeviceToHost, st));
-  SGM_HIP_TRY(s, hipEventRecord(s->ev[3], st));
-  SGM_HIP_TRY(s, hipStreamSynchronize(st));
+  PBA_HIP_TRY(s, hipGetLastError());
+  PBA_HIP_TRY(s, hipEventRecord(s->ev[2], st));
+  if (disp_scaled) PBA_HIP_TRY(s, hipMemcpyAsync(s->h_disp, s->d_disp, npix * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+  if (disparity) PBA_HIP_TRY(s, hipMemcpyAsync(s->h_disparity, s->d_disparity, npix * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (depth) PBA_HIP_TRY(s, hipMemcpyAsync(s->h_depth, s->d_depth, npix * sizeof(float), hipMemcpyDeviceToHost, st));
+  PBA_HIP_TRY(s, hipEventRecord(s->ev[3], st));
+  PBA_HIP_TRY(s, hipStreamSynchronize(st));
   if (disp_scaled) std::memcpy(disp_scaled, s->h_disp, npix * sizeof(uint16_t));
   if (disparity) std::memcpy(disparity, s->h_disparity, npix * sizeof(float));
   if (depth) std::memcpy(depth, s->h_depth, npix * sizeof(float));
@@ -587,8 +531,8 @@ int pba_sgm_compute(pba_sgm* s, const uint8_t* left, const uint8_t* right, float
 int pba_sgm_get_timing(pba_sgm* s, float* kernels_ms, float* total_ms) {
   if (!s) return PBA_ERR_INVALID;
   if (!s->computed) return fail(s, PBA_ERR_STATE, "pba_sgm_get_timing before pba_sgm_compute");
-  if (kernels_ms) SGM_HIP_TRY(s, hipEventElapsedTime(kernels_ms, s->ev[1], s->ev[2]));
-  if (total_ms) SGM_HIP_TRY(s, hipEventElapsedTime(total_ms, s->ev[0], s->ev[3]));
+  if (kernels_ms) PBA_HIP_TRY(s, hipEventElapsedTime(kernels_ms, s->ev[1], s->ev[2]));
+  if (total_ms) PBA_HIP_TRY(s, hipEventElapsedTime(total_ms, s->ev[0], s->ev[3]));
   return PBA_OK;
 }
 
@@ -612,8 +556,8 @@ int pba_sgm_get_stage(pba_sgm* s, int32_t stage, void* buf) {
     case PBA_SGM_STAGE_DISP_RIGHT_FILTERED: src = s->d_filtered + npix; bytes = npix * sizeof(uint16_t); break;
     default: return fail(s, PBA_ERR_INVALID, "pba_sgm_get_stage: unknown stage %d", stage);
   }
-  SGM_HIP_TRY(s, hipSetDevice(s->device));
-  SGM_HIP_TRY(s, hipMemcpy(buf, src, bytes, hipMemcpyDeviceToHost));
+  PBA_HIP_TRY(s, hipSetDevice(s->device));
+  PBA_HIP_TRY(s, hipMemcpy(buf, src, bytes, hipMemcpyDeviceToHost));
   return PBA_OK;
 }
 

@@ -18,13 +18,11 @@
 
 #include <algorithm>
 #include <climits>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
 
 #include "../../include/pba_stereo.h"
+#include "pba_handle.h"
 
 namespace {
 
@@ -217,27 +215,14 @@ __global__ __launch_bounds__(256) void k_stereo_bm(const uint8_t* __restrict__ p
   }
 }
 
-thread_local std::string g_create_err;
-
-int create_fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_create_err = buf;
-  return code;
-}
-
 }  // namespace
 
-struct pba_stereo {
-  int rows = 0, cols = 0, device = 0;
+struct pba_stereo : pba::Handle {      // (device, stream, err, mem, events)
+  int rows = 0, cols = 0;
   pba_stereo_bm_params p{};
   Roi roi{};
   bool staged = false;
   size_t lds = 0;
-  hipStream_t stream = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // upload start, kernels start, kernels end, copy-back end
   uint8_t* d_img = nullptr;      // left, right
   uint8_t* d_pf = nullptr;       // prefiltered left, right
@@ -247,26 +232,12 @@ struct pba_stereo {
   int16_t* h_disp = nullptr;     // pinned copy-back buffers
   float* h_depth = nullptr;
   bool computed = false;
-  std::string err;
 };
 
 namespace {
 
-int fail(pba_stereo* s, int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  s->err = buf;
-  return code;
-}
-
-#define STEREO_HIP_TRY(s, call)                                                                  \
-  do {                                                                                           \
-    hipError_t _r = (call);                                                                      \
-    if (_r != hipSuccess) return fail((s), PBA_ERR_HIP, "%s: %s", #call, hipGetErrorString(_r)); \
-  } while (0)
+using pba::MemKind;      // (fail and create_bail are found through the handle argument)
+constexpr auto create_fail = pba::create_fail<pba_stereo>;
 
 // the checks of OpenCV 2.4 cvFindStereoCorrespondenceBM that apply, plus the options this matcher does not build
 int validate(int32_t rows, int32_t cols, const pba_stereo_bm_params* p) {
@@ -327,23 +298,9 @@ int pba_stereo_validate_params(int32_t rows, int32_t cols, const pba_stereo_bm_p
   return validate(rows, cols, p);
 }
 
-const char* pba_stereo_last_error(const pba_stereo* s) { return s ? s->err.c_str() : g_create_err.c_str(); }
+const char* pba_stereo_last_error(const pba_stereo* s) { return s ? s->err.c_str() : pba::create_error<pba_stereo>().c_str(); }
 
-void pba_stereo_destroy(pba_stereo* s) {
-  if (!s) return;
-  if (s->stream) (void)hipStreamSynchronize(s->stream);
-  for (hipEvent_t& e : s->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (s->d_img) (void)hipFree(s->d_img);
-  if (s->d_pf) (void)hipFree(s->d_pf);
-  if (s->d_disp) (void)hipFree(s->d_disp);
-  if (s->d_depth) (void)hipFree(s->d_depth);
-  if (s->h_img) (void)hipHostFree(s->h_img);
-  if (s->h_disp) (void)hipHostFree(s->h_disp);
-  if (s->h_depth) (void)hipHostFree(s->h_depth);
-  if (s->stream) (void)hipStreamDestroy(s->stream);
-  delete s;
-}
+void pba_stereo_destroy(pba_stereo* s) { pba::handle_destroy(s); }
 
 int pba_stereo_create(int32_t rows, int32_t cols, const pba_stereo_bm_params* p, int32_t device, pba_stereo** out) {
   if (!out) return create_fail(PBA_ERR_INVALID, "out is NULL");
@@ -352,15 +309,11 @@ int pba_stereo_create(int32_t rows, int32_t cols, const pba_stereo_bm_params* p,
   if (rows == 0 && cols == 0) return create_fail(PBA_ERR_INVALID, "image size 0 x 0");
   int rc = validate(rows, cols, p);
   if (rc) return rc;
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || device < 0 || device >= n_dev) {
-    (void)hipGetLastError();
+  if (!pba::device_exists(device))
     return create_fail(PBA_ERR_NO_DEVICE, "no HIP device %d (the stereo matcher has no CPU fallback)", device);
-  }
   pba_stereo* s = new pba_stereo();
   s->rows = rows;
   s->cols = cols;
-  s->device = device;
   s->p = *p;
   const int r = p->sad_window_size / 2;
   const int min_d = p->min_disparity, max_d = min_d + p->number_of_disparities - 1;
@@ -374,25 +327,16 @@ int pba_stereo_create(int32_t rows, int32_t cols, const pba_stereo_bm_params* p,
   const size_t staged = (size_t)(kTY + 2 * r) * (2 * (kTX + 2 * r) + p->number_of_disparities - 1);
   s->staged = hbytes + staged <= kLdsBudget;
   s->lds = s->staged ? hbytes + staged : hbytes;
-  auto bail = [&](int code) {
-    g_create_err = s->err;
-    pba_stereo_destroy(s);
-    return code;
-  };
   const size_t npix = (size_t)rows * cols;
-  if (hipSetDevice(device) != hipSuccess) return bail(fail(s, PBA_ERR_HIP, "hipSetDevice(%d) failed", device));
-  if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(s, PBA_ERR_HIP, "hipStreamCreate failed"));
+  if ((rc = pba::handle_open(s, device))) return create_bail(s, rc, pba_stereo_destroy);
   for (hipEvent_t& e : s->ev)
-    if (hipEventCreate(&e) != hipSuccess) return bail(fail(s, PBA_ERR_HIP, "hipEventCreate failed"));
-  if (hipMalloc(reinterpret_cast<void**>(&s->d_img), 2 * npix) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&s->d_pf), 2 * npix) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&s->d_disp), npix * sizeof(int16_t)) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&s->d_depth), npix * sizeof(float)) != hipSuccess)
-    return bail(fail(s, PBA_ERR_HIP, "device allocation of %zu pixels failed", npix));
-  if (hipHostMalloc(reinterpret_cast<void**>(&s->h_img), 2 * npix, hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void**>(&s->h_disp), npix * sizeof(int16_t), hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void**>(&s->h_depth), npix * sizeof(float), hipHostMallocDefault) != hipSuccess)
-    return bail(fail(s, PBA_ERR_HIP, "pinned host allocation of %zu pixels failed", npix));
+    if ((rc = pba::handle_event(s, &e))) return create_bail(s, rc, pba_stereo_destroy);
+  if (s->mem.reserve(&s->d_img, MemKind::device, 2 * npix) || s->mem.reserve(&s->d_pf, MemKind::device, 2 * npix) ||
+      s->mem.reserve(&s->d_disp, MemKind::device, npix) || s->mem.reserve(&s->d_depth, MemKind::device, npix))
+    return create_bail(s, fail(s, PBA_ERR_HIP, "device allocation of %zu pixels failed", npix), pba_stereo_destroy);
+  if (s->mem.reserve(&s->h_img, MemKind::pinned, 2 * npix) || s->mem.reserve(&s->h_disp, MemKind::pinned, npix) ||
+      s->mem.reserve(&s->h_depth, MemKind::pinned, npix))
+    return create_bail(s, fail(s, PBA_ERR_HIP, "pinned host allocation of %zu pixels failed", npix), pba_stereo_destroy);
   *out = s;
   return PBA_OK;
 }
@@ -400,7 +344,7 @@ int pba_stereo_create(int32_t rows, int32_t cols, const pba_stereo_bm_params* p,
 int pba_stereo_compute(pba_stereo* s, const uint8_t* left, const uint8_t* right, float bf, int16_t* disp16, float* depth) {
   if (!s) return PBA_ERR_INVALID;
   if (!left || !right) return fail(s, PBA_ERR_INVALID, "pba_stereo_compute: left and right must not be NULL");
-  STEREO_HIP_TRY(s, hipSetDevice(s->device));
+  PBA_HIP_TRY(s, hipSetDevice(s->device));
   const int H = s->rows, W = s->cols;
   const size_t npix = (size_t)H * W;
   const pba_stereo_bm_params& p = s->p;
@@ -409,12 +353,12 @@ int pba_stereo_compute(pba_stereo* s, const uint8_t* left, const uint8_t* right,
   // the caller's buffers are only borrowed: one pinned staging copy, then an async upload (pageable copy + sync is much slower)
   std::memcpy(s->h_img, left, npix);
   std::memcpy(s->h_img + npix, right, npix);
-  STEREO_HIP_TRY(s, hipEventRecord(s->ev[0], s->stream));
-  STEREO_HIP_TRY(s, hipMemcpyAsync(s->d_img, s->h_img, 2 * npix, hipMemcpyHostToDevice, s->stream));
-  STEREO_HIP_TRY(s, hipEventRecord(s->ev[1], s->stream));
+  PBA_HIP_TRY(s, hipEventRecord(s->ev[0], s->stream));
+  PBA_HIP_TRY(s, hipMemcpyAsync(s->d_img, s->h_img, 2 * npix, hipMemcpyHostToDevice, s->stream));
+  PBA_HIP_TRY(s, hipEventRecord(s->ev[1], s->stream));
   hipLaunchKernelGGL(k_stereo_prefilter, dim3((W + 255) / 256, H, 2), dim3(256), 0, s->stream, s->d_img, s->d_pf, H, W,
                      p.pre_filter_cap, s->d_disp, d_depth, s->roi, filtered, bf);
-  STEREO_HIP_TRY(s, hipGetLastError());
+  PBA_HIP_TRY(s, hipGetLastError());
   if (s->roi.x0 < s->roi.x1 && s->roi.y0 < s->roi.y1) {
     const dim3 grid((s->roi.x1 - s->roi.x0 + kTX - 1) / kTX, (s->roi.y1 - s->roi.y0 + kTY - 1) / kTY);
     const int r = p.sad_window_size / 2;
@@ -424,13 +368,13 @@ int pba_stereo_compute(pba_stereo* s, const uint8_t* left, const uint8_t* right,
     else
       hipLaunchKernelGGL(k_stereo_bm<false>, grid, dim3(kThreads), s->lds, s->stream, s->d_pf, H, W, r, p.pre_filter_cap, p.min_disparity,
                          p.number_of_disparities, p.texture_threshold, p.uniqueness_ratio, s->roi, s->d_disp, d_depth, bf);
-    STEREO_HIP_TRY(s, hipGetLastError());
+    PBA_HIP_TRY(s, hipGetLastError());
   }
-  STEREO_HIP_TRY(s, hipEventRecord(s->ev[2], s->stream));
-  if (disp16) STEREO_HIP_TRY(s, hipMemcpyAsync(s->h_disp, s->d_disp, npix * sizeof(int16_t), hipMemcpyDeviceToHost, s->stream));
-  if (depth) STEREO_HIP_TRY(s, hipMemcpyAsync(s->h_depth, s->d_depth, npix * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-  STEREO_HIP_TRY(s, hipEventRecord(s->ev[3], s->stream));
-  STEREO_HIP_TRY(s, hipStreamSynchronize(s->stream));
+  PBA_HIP_TRY(s, hipEventRecord(s->ev[2], s->stream));
+  if (disp16) PBA_HIP_TRY(s, hipMemcpyAsync(s->h_disp, s->d_disp, npix * sizeof(int16_t), hipMemcpyDeviceToHost, s->stream));
+  if (depth) PBA_HIP_TRY(s, hipMemcpyAsync(s->h_depth, s->d_depth, npix * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+  PBA_HIP_TRY(s, hipEventRecord(s->ev[3], s->stream));
+  PBA_HIP_TRY(s, hipStreamSynchronize(s->stream));
   if (disp16) std::memcpy(disp16, s->h_disp, npix * sizeof(int16_t));
   if (depth) std::memcpy(depth, s->h_depth, npix * sizeof(float));
   s->computed = true;
@@ -441,18 +385,18 @@ int pba_stereo_get_prefiltered(pba_stereo* s, uint8_t* left, uint8_t* right) {
   if (!s) return PBA_ERR_INVALID;
   if (!left || !right) return fail(s, PBA_ERR_INVALID, "pba_stereo_get_prefiltered: NULL output");
   if (!s->computed) return fail(s, PBA_ERR_STATE, "pba_stereo_get_prefiltered before pba_stereo_compute");
-  STEREO_HIP_TRY(s, hipSetDevice(s->device));
+  PBA_HIP_TRY(s, hipSetDevice(s->device));
   const size_t npix = (size_t)s->rows * s->cols;
-  STEREO_HIP_TRY(s, hipMemcpy(left, s->d_pf, npix, hipMemcpyDeviceToHost));
-  STEREO_HIP_TRY(s, hipMemcpy(right, s->d_pf + npix, npix, hipMemcpyDeviceToHost));
+  PBA_HIP_TRY(s, hipMemcpy(left, s->d_pf, npix, hipMemcpyDeviceToHost));
+  PBA_HIP_TRY(s, hipMemcpy(right, s->d_pf + npix, npix, hipMemcpyDeviceToHost));
   return PBA_OK;
 }
 
 int pba_stereo_get_timing(pba_stereo* s, float* kernels_ms, float* total_ms) {
   if (!s) return PBA_ERR_INVALID;
   if (!s->computed) return fail(s, PBA_ERR_STATE, "pba_stereo_get_timing before pba_stereo_compute");
-  if (kernels_ms) STEREO_HIP_TRY(s, hipEventElapsedTime(kernels_ms, s->ev[1], s->ev[2]));
-  if (total_ms) STEREO_HIP_TRY(s, hipEventElapsedTime(total_ms, s->ev[0], s->ev[3]));
+  if (kernels_ms) PBA_HIP_TRY(s, hipEventElapsedTime(kernels_ms, s->ev[1], s->ev[2]));
+  if (total_ms) PBA_HIP_TRY(s, hipEventElapsedTime(total_ms, s->ev[0], s->ev[3]));
   return PBA_OK;
 }
 
