@@ -243,8 +243,9 @@ int pba_frontend_zncc_probe(pba_engine* e, int32_t n, const double* uv, const fl
  * Call order: pba_set_frame_u8 (every slot the observation list uses), pba_set_problem and pba_set_cameras may come in
  * any order, all three before pba_linearize / pba_solve; a pass that finds one of them missing, an observation whose
  * slot is >= n_frames, or a slot without an uploaded frame returns PBA_ERR_STATE (nothing is launched).
- * Limit: at most 32 FREE cameras (n_frames <= max_frames <= PBA_MAX_FRAMES).  The window shape picks the path at
- * pba_set_cameras: up to 15 free cameras the narrow kernels and drivers, 16 to 32 the wide chain (host-stepped driver).
+ * Limit: at most 32 slots (n_frames <= max_frames <= PBA_MAX_FRAMES).  The window shape picks the path at pba_set_cameras /
+ * pba_set_cameras_anchored: a window of at most 16 slots with at most 15 free cameras runs the narrow kernels and drivers, one
+ * with more slots or with 16 to 32 free cameras the wide chain (host-stepped driver).
  * A wide window refuses the multi-rank transports (pba_comm_*), the inverse-depth mode and the precision-sweep flags:
  * PBA_ERR_INVALID with a message in pba_last_error, whichever of the calls comes second.
  * pba_set_points_constant (after pba_set_problem, before or after pba_set_cameras / pba_set_inverse_depth) turns the passes
@@ -253,6 +254,22 @@ int pba_set_problem(pba_engine* e, int32_t n_points, const double* xyz, const do
                     int32_t n_obs, const int32_t* obs_point, const int32_t* obs_slot, const double* weights);
 /* cams6: [n_frames][6]; fixed_slot: SetParameterBlockConstant (photobundle.cc:809-813), -1 for none. */
 int pba_set_cameras(pba_engine* e, const double* cams6, int32_t n_frames, int32_t fixed_slot);
+/* Any set of constant cameras (anchor frames of a local bundle adjustment).  Bit c of anchor_mask set: slot c is constant, the Ceres
+ * call SetParameterBlockConstant on that camera block.  pba_set_cameras(e, cams6, n, fixed_slot) IS this call with
+ * anchor_mask = fixed_slot < 0 ? 0 : 1u << fixed_slot: same launches, same bits, on every driver.  Semantics are Ceres' for the reduced
+ * program.  Full mode: the camera columns are the slots outside the mask in ascending slot order (pba_get_reduced_system returns
+ * n = 6 x the number of free slots); every residual block stays, because each depends on a free point, and a constant camera's blocks
+ * still feed the point blocks; summary.fixed_cost = 0; gradient norms, step_norm and x_norm run over the free cameras that have
+ * residual blocks and over all points.  Anchored cameras are never written: pba_get_state returns them byte for byte as set.
+ * Pose-only mode (pba_set_points_constant): the blocks of every anchored camera leave the program, summary.fixed_cost is their
+ * loss-corrected cost summed in ascending slot order, the counts are the program's.  Structure-only mode (pba_set_cameras_constant):
+ * the mask has no effect.  The inverse-depth mode and pba_solve_batch take anchored narrow windows.
+ * PBA_ERR_INVALID with a message in pba_last_error: bits at or above n_frames; in the full mode a mask that covers every slot (use
+ * pba_set_cameras_constant), whichever of this call and the switch back from a constant mode comes second -- such a mask is legal
+ * while a constant mode is on, and a pba_set_problem that ends the mode under it makes the passes return PBA_ERR_STATE until the
+ * cameras are set again; a mask of two or more bits together with a multi-rank transport (pba_comm_*) or the precision-sweep flags,
+ * whichever call comes second.  After a refused call the engine holds what it held before. */
+int pba_set_cameras_anchored(pba_engine* e, const double* cams6, int32_t n_frames, uint32_t anchor_mask);
 /* Inverse-depth variant of the point parameterisation (named by the project's north star; the REFERENCE optimises free
  * world points, photobundle.cc:692/:795, so this mode has no reference counterpart and is outside every parity claim).
  * Call after pba_set_problem: point i then lives on the fixed world ray rays6[i] = {origin (3), direction (3)} with the
@@ -262,9 +279,9 @@ int pba_set_cameras(pba_engine* e, const double* cams6, int32_t n_frames, int32_
 int pba_set_inverse_depth(pba_engine* e, const double* rays6, const double* rho);
 int pba_get_points_world(pba_engine* e, double* xyz);
 /* Pose-only solves.  Ceres: SetParameterBlockConstant on every point block.  on != 0: pba_linearize / pba_step / pba_accept / pba_solve
- * treat every point as constant; cameras other than fixed_slot stay free.  Call after pba_set_problem; pba_set_problem switches it off
+ * treat every point as constant; cameras outside the anchor mask (other than fixed_slot) stay free.  Call after pba_set_problem; pba_set_problem switches it off
  * again (as it does for inverse depth).  Semantics are Ceres' for the reduced program: its parameter blocks are the free cameras that
- * have at least one residual block; the residual blocks of the constant camera leave the program and their loss-corrected cost is
+ * have at least one residual block; the residual blocks of the constant cameras leave the program and their loss-corrected cost is
  * summary.fixed_cost (initial_cost and final_cost include it; the per-iteration cost, num_residual_blocks and num_residuals count the
  * program only; pba_linearize's cost stays the sum over ALL residual blocks).  The normal equations are block diagonal, one 6x6 block
  * per free camera solved by an exact Cholesky, at every window shape (2..32 slots); gradient norms, step_norm, x_norm and
@@ -275,7 +292,7 @@ int pba_get_points_world(pba_engine* e, double* xyz);
  * windows of 16..32 free cameras, what pba_set_cameras refuses there).  Switched off again the engine solves as a fresh one does. */
 int pba_set_points_constant(pba_engine* e, int32_t on);
 /* Structure-only solves.  Ceres: SetParameterBlockConstant on every camera block.  on != 0: pba_linearize / pba_step / pba_accept /
- * pba_solve treat every camera as constant and refine the points against them; fixed_slot of pba_set_cameras has no effect.  Call
+ * pba_solve treat every camera as constant and refine the points against them; fixed_slot of pba_set_cameras (the anchor mask) has no effect.  Call
  * order and lifetime are pba_set_points_constant's.  Semantics are Ceres' for the reduced program: its parameter blocks are the points,
  * every residual block stays in it (summary.fixed_cost = 0, num_residual_blocks and num_residuals count every block).  The normal
  * equations are block diagonal, one 3x3 block per point (1x1 in the inverse-depth mode) solved by an exact Cholesky, at every window

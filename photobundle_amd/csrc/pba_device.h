@@ -5,6 +5,7 @@
 
 #include "../../include/pba.h"
 #include "pba_lm_rules.h"      // the scalar block of a step (Scal), LmState and the trust-region rules
+#include "pba_slot_rule.h"     // anchor mask -> (is_free, free_index) of a window slot
 
 namespace pba {
 
@@ -34,7 +35,7 @@ struct CamGeom {
   double R[9];
   double dR[27];
   int32_t rodrigues;  // theta^2 > DBL_EPSILON
-  int32_t is_free;    // 0 for the constant camera
+  int32_t is_free;    // 0 for a constant (anchored) camera
   int32_t free_index; // index among free cameras, -1 if constant
   int32_t pad;
 };

@@ -58,7 +58,8 @@ struct pba_engine : pba::Handle {      // (device, stream, err, mem, events)
   uint32_t slot_mask = 0;           // window slots referenced by the observation list
 
   // problem
-  int n_points = 0, n_obs = 0, n_frames = 0, fixed_slot = -1, n_free = 0;
+  int n_points = 0, n_obs = 0, n_frames = 0, n_free = 0;
+  uint32_t anchor_mask = 0;         // constant slots (pba_set_cameras_anchored; pba_slot_rule.h turns it into free indices)
   bool have_problem = false, have_cams = false, have_lin = false;
   bool lin_valid[2] = {false, false};   // rec[k] holds a Jacobian pass of point k
   bool speculate = true;            // candidate pass = Jacobian pass (skips the re-linearisation after an accept)
@@ -140,7 +141,8 @@ struct pba_engine : pba::Handle {      // (device, stream, err, mem, events)
   int dbg_left = 0;
   int n_pairs = 0, part_stride = 0;
   static constexpr int kChunks = 32;
-  // wide windows (kWideMinFree..kMaxFramesWide free cameras, pba_wide.h): chosen by pba_set_cameras from the window shape
+  // wide windows (more than kMaxFrames slots, or kWideMinFree..kMaxFramesWide free cameras; pba_wide.h): chosen by pba_set_cameras_anchored
+  // from the window shape
   bool wide = false;
   bool wide_ready = false;          // the co-observation lists below match the current problem and camera set
   std::vector<int32_t> h_pt_begin;  // host copies of the observation structure
@@ -229,11 +231,16 @@ int host_alloc(pba_engine* e, T** p, size_t n, T** dev_view = nullptr) {
   return PBA_OK;
 }
 
+// the engine is in the full mode (cameras and points free) with every slot anchored: no camera column is left
+bool full_mode_all_anchored(const pba_engine* e) { return e->have_cams && e->n_free == 0 && !e->points_const && !e->cams_const; }
+
 // Call-order / consistency check before any pass touches the device (include/pba.h: PBA_ERR_STATE).
 int check_ready(pba_engine* e, const char* who) {
   if (e->poisoned) return fail(e, PBA_ERR_STATE, "%s: the engine is unusable after a timed-out step (stalled stream / collective); destroy it", who);
   if (!e->have_problem || !e->have_cams)
     return fail(e, PBA_ERR_STATE, "call order violated: %s before set_problem/set_cameras", who);
+  if (full_mode_all_anchored(e))      // (pba_set_problem switched a constant mode off under a mask that was legal in it)
+    return fail(e, PBA_ERR_STATE, "%s: the anchor mask covers all %d slots and no constant mode is on; set the cameras again", who, e->n_frames);
   for (int s = 0; s < kMaxFramesWide; ++s) {
     if (!((e->slot_mask >> s) & 1u)) continue;
     if (s >= e->n_frames) return fail(e, PBA_ERR_STATE, "call order violated: an observation uses slot %d but only %d cameras are set", s, e->n_frames);
@@ -465,8 +472,8 @@ void launch_schur(pba_engine* e, const SchurParams& sp) {
 // cut into chunks of kWideChunk.  A causal window is banded: pairs of cameras far apart share few points or none.
 int wide_prepare(pba_engine* e) {
   if (e->wide_ready) return PBA_OK;
-  const int nf = e->n_free, fixed = e->fixed_slot, n_pairs = e->n_pairs;
-  auto free_of = [&](int s) { return s == fixed ? -1 : (fixed >= 0 && s > fixed ? s - 1 : s); };
+  const int nf = e->n_free, n_pairs = e->n_pairs;
+  auto free_of = [&](int s) { return slot_free_index(e->anchor_mask, s); };
   auto pair_of = [&](int a, int b) { return a * nf - a * (a - 1) / 2 + (b - a); };
   std::vector<int64_t> off((size_t)n_pairs + 1, 0);
   int fa[kMaxFramesWide], lo[kMaxFramesWide];
@@ -626,7 +633,7 @@ SolveParams solve_params(pba_engine* e, int cur, int init_scale, const pba_solve
   SolveParams so{};
   so.packed = e->d_packed; so.cams = e->d_cams[cur]; so.cams_cand = e->d_cams[cand]; so.delta_c = e->d_delta_c;
   so.sc = e->d_sc; so.S_dbg = (e->cfg.flags & 1) ? e->d_S : nullptr; so.rhs_dbg = e->d_rhs; so.scal = e->d_scal; so.geom = e->d_geom[cur];
-  so.n_frames = e->n_frames; so.n_free = e->n_free; so.n_pairs = e->n_pairs; so.stride = e->part_stride; so.fixed_slot = e->fixed_slot; so.tab = e->d_solve_tab;
+  so.n_frames = e->n_frames; so.n_free = e->n_free; so.n_pairs = e->n_pairs; so.stride = e->part_stride; so.anchor_mask = e->anchor_mask; so.tab = e->d_solve_tab;
   so.geom_cand = with_cand ? e->d_geom[cand] : nullptr;
   so.init_scale = init_scale; so.jacobi = o->jacobi_scaling; so.radius = radius; so.min_diag = o->min_lm_diagonal; so.max_diag = o->max_lm_diagonal;
   return so;
@@ -1292,15 +1299,39 @@ int pba_set_problem(pba_engine* e, int32_t n_points, const double* xyz, const do
   return PBA_OK;
 }
 
+// Two or more anchored slots are a single-rank, exact-sampler feature (nullptr: the engine may run them)
+static const char* anchors_refusal(const pba_engine* e) {
+  if (e->comm.multi()) return "multi-rank solves (pba_comm_*) take at most one constant slot";
+  if ((e->cfg.flags >> 1) & 3) return "the precision-sweep sampler modes (pba_config.flags bits 1-2) take at most one constant slot";
+  return nullptr;
+}
 int pba_set_cameras(pba_engine* e, const double* cams6, int32_t n_frames, int32_t fixed_slot) {
   if (!e || !cams6 || n_frames < 2 || n_frames > e->cfg.max_frames || fixed_slot >= n_frames) return PBA_ERR_INVALID;
+  return pba_set_cameras_anchored(e, cams6, n_frames, slot_mask_of_fixed(fixed_slot));
+}
+
+int pba_set_cameras_anchored(pba_engine* e, const double* cams6, int32_t n_frames, uint32_t anchor_mask) {
+  if (!e || !cams6 || n_frames < 2 || n_frames > e->cfg.max_frames || n_frames > kMaxFramesWide) return PBA_ERR_INVALID;
+  if (n_frames < 32 && (anchor_mask >> n_frames))
+    return fail(e, PBA_ERR_INVALID, "pba_set_cameras_anchored: anchor_mask 0x%x has bits at or above n_frames = %d", anchor_mask, n_frames);
+  const int nf = slot_count_free(anchor_mask, n_frames);
+  if (nf == 0 && !e->points_const && !e->cams_const)
+    return fail(e, PBA_ERR_INVALID, "pba_set_cameras_anchored: anchor_mask covers all %d slots: no camera is left to solve for; hold every "
+                                    "camera constant with pba_set_cameras_constant", n_frames);
+  if (n_frames - nf >= 2) {
+    const char* why = anchors_refusal(e);
+    if (why) return fail(e, PBA_ERR_INVALID, "pba_set_cameras_anchored: %d constant slots: %s", n_frames - nf, why);
+  }
   PBA_ENTER(e);
+  // the window shape picks the path: the narrow kernels stage kMaxFrames-slot camera tables and hold up to kWideMinFree - 1 free
+  // cameras; a window with more slots or more free cameras runs the wide chain
+  const bool wide = n_frames > kMaxFrames || nf >= kWideMinFree;
   {
-    // the window shape picks the path: up to kWideMinFree - 1 free cameras the narrow kernels, beyond them the wide chain
-    const int nf = n_frames - (fixed_slot >= 0 ? 1 : 0);
-    const char* why = nf >= kWideMinFree ? wide_refusal(e) : nullptr;
-    if (why) return fail(e, PBA_ERR_INVALID, "pba_set_cameras: %d free cameras: %s (at most %d free cameras there)", nf, why, kWideMinFree - 1);
-    if (nf >= kWideMinFree) {
+    const char* why = wide ? wide_refusal(e) : nullptr;
+    if (why && nf >= kWideMinFree)
+      return fail(e, PBA_ERR_INVALID, "pba_set_cameras: %d free cameras: %s (at most %d free cameras there)", nf, why, kWideMinFree - 1);
+    if (why) return fail(e, PBA_ERR_INVALID, "pba_set_cameras: %d slots: %s (at most %d slots there)", n_frames, why, kMaxFrames);
+    if (wide) {
       int lds_max = 0;
       const size_t need = solve_wide_smem_bytes(6 * nf) + 1024;
       if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, e->cfg.device) == hipSuccess && lds_max > 0 && need > (size_t)lds_max)
@@ -1310,11 +1341,11 @@ int pba_set_cameras(pba_engine* e, const double* cams6, int32_t n_frames, int32_
     }
   }
   e->n_frames = n_frames;
-  e->fixed_slot = fixed_slot < 0 ? -1 : fixed_slot;
-  e->n_free = n_frames - (e->fixed_slot >= 0 ? 1 : 0);
+  e->anchor_mask = anchor_mask;
+  e->n_free = nf;
   e->n_pairs = e->n_free * (e->n_free + 1) / 2;
   e->part_stride = 36 * e->n_pairs + 3 * 6 * e->n_free + 3;
-  e->wide = e->n_free >= kWideMinFree;
+  e->wide = wide;
   e->wide_ready = false;
   int rc;
   if (e->wide) {
@@ -1342,7 +1373,7 @@ int pba_set_cameras(pba_engine* e, const double* cams6, int32_t n_frames, int32_
     e->solve_tab_nf = e->n_free;
   }
   HIP_TRY(e, hipMemcpyAsync(e->d_cams[e->cur], cams6, sizeof(double) * 6 * n_frames, hipMemcpyHostToDevice, e->stream));
-  hipLaunchKernelGGL(k_cam_geom, dim3(1), dim3(64), 0, e->stream, e->d_cams[e->cur], e->d_geom[e->cur], n_frames, e->fixed_slot);
+  hipLaunchKernelGGL(k_cam_geom, dim3(1), dim3(64), 0, e->stream, e->d_cams[e->cur], e->d_geom[e->cur], n_frames, e->anchor_mask);
   HIP_TRY(e, hipGetLastError());
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   e->have_cams = true;
@@ -1419,6 +1450,9 @@ int pba_set_points_constant(pba_engine* e, int32_t on) {
     if (e->cams_const)
       return fail(e, PBA_ERR_INVALID, "pba_set_points_constant: the cameras-constant mode (pba_set_cameras_constant) is on: with every block constant the program is empty");
   }
+  if (!on && e->have_cams && e->n_free == 0 && e->points_const && !e->cams_const)
+    return fail(e, PBA_ERR_INVALID, "pba_set_points_constant(0): the anchor mask covers all %d slots (pba_set_cameras_anchored): no camera is left to solve "
+                                    "for; set other cameras first, or hold every camera constant with pba_set_cameras_constant", e->n_frames);
   e->points_const = on != 0;
   e->pose_xyz_synced = false; e->pose_sums_cur = -1;
   e->have_lin = false;
@@ -1451,6 +1485,9 @@ int pba_set_cameras_constant(pba_engine* e, int32_t on) {
     const char* why = points_refusal(e);
     if (why) return fail(e, PBA_ERR_INVALID, "pba_set_cameras_constant: %s", why);
   }
+  if (!on && e->have_cams && e->n_free == 0 && e->cams_const && !e->points_const)
+    return fail(e, PBA_ERR_INVALID, "pba_set_cameras_constant(0): the anchor mask covers all %d slots (pba_set_cameras_anchored): no camera is left to solve "
+                                    "for; set other cameras first, or hold every camera constant with pba_set_cameras_constant", e->n_frames);
   e->cams_const = on != 0;
   e->pts_cams_synced = false; e->pts_sys_cur = -1; e->pts_dbg_valid = false;
   e->have_lin = false;
@@ -1618,7 +1655,7 @@ static int pose_step(pba_engine* e, double radius, int32_t init_scale, const pba
   so.S_dbg = (e->cfg.flags & 1) ? e->d_S : nullptr; so.rhs_dbg = e->d_rhs; so.scal = e->d_scal;
   so.geom = e->d_geom[cur]; so.geom_cand = e->d_geom[cand];
   so.n_parts = e->pose_grid; so.n_cost_blocks = e->cost_blocks[cur]; so.reduce = reduce ? 1 : 0;
-  so.n_frames = e->n_frames; so.n_free = e->n_free; so.fixed_slot = e->fixed_slot; so.init_scale = init_scale; so.jacobi = o->jacobi_scaling;
+  so.n_frames = e->n_frames; so.n_free = e->n_free; so.anchor_mask = e->anchor_mask; so.init_scale = init_scale; so.jacobi = o->jacobi_scaling;
   so.grad_only = grad_only; so.radius = radius; so.min_diag = o->min_lm_diagonal; so.max_diag = o->max_lm_diagonal;
   ev_begin(e, 3);
   hipLaunchKernelGGL(k_pose_solve, dim3(1), dim3(kPoseThreads), 0, e->stream, so);
@@ -1764,7 +1801,7 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
     bs.pt_begin = e->d_pt_begin; bs.obs_slot = e->d_obs_slot; bs.sp = e->d_sp; bs.ptrec = e->d_ptrec;
     bs.delta_c = e->d_delta_c; bs.block_out = e->d_bs_out; bs.rec_stride = e->rec_stride; bs.n_points = e->n_points;
     bs.fx = e->cfg.fx; bs.fy = e->cfg.fy;
-    bs.cams_cand = e->d_cams[cand]; bs.geom_cand = e->d_geom[cand]; bs.n_frames = e->n_frames; bs.fixed_slot = e->fixed_slot;
+    bs.cams_cand = e->d_cams[cand]; bs.geom_cand = e->d_geom[cand]; bs.n_frames = e->n_frames; bs.anchor_mask = e->anchor_mask;
     hipLaunchKernelGGL(k_backsub, dim3(e->backsub_grid), dim3(256), 0, e->stream, bs);
     // candidate point: Jacobian pass when speculating on acceptance, else cost pass
     SampleParams sp = make_sample_params(e, cand);
@@ -1843,6 +1880,8 @@ int pba_comm_init_rccl(pba_engine* e, const void* id128, int32_t rank, int32_t w
     return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for the points-constant mode (pba_set_points_constant)");
   if (world > 1 && e->cams_const)
     return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for the cameras-constant mode (pba_set_cameras_constant)");
+  if (world > 1 && e->have_cams && e->n_frames - e->n_free >= 2)
+    return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves take at most one constant slot (pba_set_cameras_anchored holds %d)", e->n_frames - e->n_free);
   PBA_ENTER(e);
   if (e->comm.init_rccl(id128, rank, world)) return fail(e, PBA_ERR_COMM, "%s", e->comm.err.c_str());
   return PBA_OK;
@@ -1856,6 +1895,8 @@ int pba_comm_init_callback(pba_engine* e, pba_allreduce_fn fn, void* ctx, int32_
     return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for the points-constant mode (pba_set_points_constant)");
   if (world > 1 && e->cams_const)
     return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for the cameras-constant mode (pba_set_cameras_constant)");
+  if (world > 1 && e->have_cams && e->n_frames - e->n_free >= 2)
+    return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves take at most one constant slot (pba_set_cameras_anchored holds %d)", e->n_frames - e->n_free);
   PBA_ENTER(e);
   if (e->comm.init_callback(fn, ctx, rank, world)) return fail(e, PBA_ERR_COMM, "%s", e->comm.err.c_str());
   return PBA_OK;
@@ -1991,12 +2032,12 @@ int pba_internal_async_capable(const pba_engine* e, const pba_solver_options* o)
 int pba_internal_points_constant(const pba_engine* e) { return e->points_const ? 1 : 0; }
 // residual blocks of the reduced program: those of the free cameras
 int64_t pba_internal_program_blocks(const pba_engine* e) {
-  if (!e->points_const || e->fixed_slot < 0) return e->n_obs;
+  if (!e->points_const || e->anchor_mask == 0) return e->n_obs;
   int64_t n = 0;
-  for (uint8_t s : e->h_obs_slot) n += (int)s != e->fixed_slot;
+  for (uint8_t s : e->h_obs_slot) n += slot_is_free(e->anchor_mask, (int)s);
   return n;
 }
-// cost of the residual blocks of the constant camera, as the last pba_step found it (0 outside the mode)
+// cost of the residual blocks of the constant cameras, as the last pba_step found it (0 outside the mode)
 double pba_internal_fixed_cost(const pba_engine* e) {
   return e->points_const ? reinterpret_cast<const volatile double*>(e->h_scal)[kPoseFixedCost] : 0.0;
 }
@@ -2259,7 +2300,7 @@ int pba_internal_resident_launch(pba_engine* e, const pba_solver_options* o, uns
   P.sp = e->d_sp; P.ptrec = e->d_ptrec; P.delta_c = e->d_delta_c; P.sc = e->d_sc; P.packed = e->d_packed; P.partial = e->d_partial;
   P.scal = e->d_scal; P.block_bs = e->d_bs_out; P.tab = e->d_solve_tab; P.rec_stride = e->rec_stride;
   P.n_tiles = e->n_tiles; P.n_obs = e->n_obs; P.n_frames = e->n_frames; P.n_free = e->n_free; P.n_pairs = e->n_pairs;
-  P.part_stride = e->part_stride; P.fixed_slot = e->fixed_slot; P.rows = e->cfg.rows; P.cols = e->cfg.cols; P.jacobi = o->jacobi_scaling;
+  P.part_stride = e->part_stride; P.anchor_mask = e->anchor_mask; P.rows = e->cfg.rows; P.cols = e->cfg.cols; P.jacobi = o->jacobi_scaling;
   P.cur0 = e->cur; P.max_num_iterations = o->max_num_iterations;
   P.fx = e->cfg.fx; P.fy = e->cfg.fy; P.cx = e->cfg.cx; P.cy = e->cfg.cy; P.huber = e->cfg.huber;
   P.min_diag = o->min_lm_diagonal; P.max_diag = o->max_lm_diagonal; P.radius0 = o->initial_trust_region_radius;

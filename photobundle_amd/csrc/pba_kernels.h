@@ -236,15 +236,15 @@ __device__ __forceinline__ void sincos_angle(double x, double& sn, double& cs) {
   }
 }
 
-__device__ inline void cam_geom_one(const double* __restrict__ cams, CamGeom* __restrict__ geom, int c, int fixed_slot) {
+__device__ inline void cam_geom_one(const double* __restrict__ cams, CamGeom* __restrict__ geom, int c, uint32_t anchor_mask) {
   CamGeom g;
   const double* p = cams + 6 * c;
   for (int k = 0; k < 3; ++k) { g.aa[k] = p[k]; g.t[k] = p[3 + k]; }
   const double wx = p[0], wy = p[1], wz = p[2];
   const double theta2 = wx * wx + wy * wy + wz * wz;
   g.rodrigues = theta2 > DBL_EPSILON;
-  g.is_free = (c != fixed_slot);
-  g.free_index = (c == fixed_slot) ? -1 : (fixed_slot >= 0 && c > fixed_slot ? c - 1 : c);
+  g.is_free = slot_is_free(anchor_mask, c);
+  g.free_index = slot_free_index(anchor_mask, c);
   g.pad = 0;
   if (g.rodrigues) {
     const double theta = sqrt(theta2);
@@ -291,9 +291,9 @@ __device__ inline void cam_geom_one(const double* __restrict__ cams, CamGeom* __
   geom[c] = g;
 }
 
-__global__ void k_cam_geom(const double* __restrict__ cams, CamGeom* __restrict__ geom, int n_frames, int fixed_slot) {
+__global__ void k_cam_geom(const double* __restrict__ cams, CamGeom* __restrict__ geom, int n_frames, uint32_t anchor_mask) {
   const int c = threadIdx.x;
-  if (c < n_frames) cam_geom_one(cams, geom, c, fixed_slot);
+  if (c < n_frames) cam_geom_one(cams, geom, c, anchor_mask);
 }
 
 // xw = R(aa) X + t in the operation order of ceres::AngleAxisRotatePoint, then Calibration::project.
@@ -2828,7 +2828,8 @@ struct BacksubParams {
   const double* cams_cand;   // candidate cameras (k_solve) -> geometry for the candidate pass, by workgroup 0
   CamGeom* geom_cand;
   int64_t rec_stride;
-  int32_t n_points, n_frames, fixed_slot;
+  int32_t n_points, n_frames;
+  uint32_t anchor_mask;
   double fx, fy;
 };
 
@@ -2836,7 +2837,7 @@ __global__ __launch_bounds__(256) void k_backsub(BacksubParams p) {
   __shared__ double s_red[3][256];
   const int tid = threadIdx.x;
   const int pt = blockIdx.x * 256 + tid;
-  if (p.geom_cand && blockIdx.x == gridDim.x - 1 && tid >= 256 - p.n_frames) cam_geom_one(p.cams_cand, p.geom_cand, 255 - tid, p.fixed_slot);
+  if (p.geom_cand && blockIdx.x == gridDim.x - 1 && tid >= 256 - p.n_frames) cam_geom_one(p.cams_cand, p.geom_cand, 255 - tid, p.anchor_mask);
   double mcc = 0.0, st2 = 0.0, x2 = 0.0;
   if (pt < p.n_points) {
     const double X[3] = {p.xyz[3 * (size_t)pt], p.xyz[3 * (size_t)pt + 1], p.xyz[3 * (size_t)pt + 2]};   // parameters

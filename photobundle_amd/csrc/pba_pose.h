@@ -117,7 +117,8 @@ struct PoseSolveParams {
   const CamGeom* geom;
   CamGeom* geom_cand;
   int32_t n_parts, n_cost_blocks, reduce;      // reduce == 0: the sums of an earlier launch are reused (re-solve after a rejected step)
-  int32_t n_frames, n_free, fixed_slot, init_scale, jacobi, grad_only;
+  int32_t n_frames, n_free, init_scale, jacobi, grad_only;
+  uint32_t anchor_mask;        // constant slots: their blocks leave the program, their cost is the fixed cost
   double radius, min_diag, max_diag;
 };
 
@@ -244,7 +245,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_solve(PoseSolveParams p) 
         p.delta_c[6 * c + i] = d[i];
         p.cams_cand[6 * c + i] = cam6[i];
       }
-      cam_geom_one(cam6 - 6 * c, p.geom_cand, c, p.fixed_slot);
+      cam_geom_one(cam6 - 6 * c, p.geom_cand, c, p.anchor_mask);
     }
     s_cam[c][0] = mcc; s_cam[c][1] = st2; s_cam[c][2] = x2; s_cam[c][3] = gmax; s_cam[c][4] = gn2; s_cam[c][5] = bad;
   }
@@ -254,7 +255,8 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_solve(PoseSolveParams p) 
     for (int c = 0; c < p.n_frames; ++c) {      // slot order
       mcc += s_cam[c][0]; st2 += s_cam[c][1]; x2 += s_cam[c][2]; gmax = fmax(gmax, s_cam[c][3]); gn2 += s_cam[c][4]; bad = fmax(bad, s_cam[c][5]);
     }
-    const double fixed = p.fixed_slot >= 0 ? s_sums[p.fixed_slot * kPoseVals + 27] : 0.0;
+    double fixed = 0.0;      // loss-corrected cost of the anchored cameras' blocks, slot order
+    for (int c = 0; c < p.n_frames; ++c) if (!slot_is_free(p.anchor_mask, c)) fixed += s_sums[c * kPoseVals + 27];
     p.scal[kMccCams] = mcc; p.scal[kStep2Cams] = st2; p.scal[kX2Cams] = x2; p.scal[kGmaxCams] = gmax; p.scal[kGnorm2Cams] = gn2;
     p.scal[kSolveOk] = bad == 0.0 ? 1.0 : 0.0;
     p.scal[kCostLin] = s_red[0] - fixed;

@@ -62,7 +62,9 @@ struct ResidentParams {
   double* block_cost[2]; int32_t* block_fail[2]; double* block_bs;
   const uint32_t* tab;
   int64_t rec_stride;
-  int32_t n_tiles, n_obs, n_frames, n_free, n_pairs, part_stride, fixed_slot, rows, cols, jacobi, cur0, max_num_iterations;
+  int32_t n_tiles, n_obs, n_frames, n_free, n_pairs, part_stride;
+  uint32_t anchor_mask;           // constant slots (pba_slot_rule.h)
+  int32_t rows, cols, jacobi, cur0, max_num_iterations;
   double fx, fy, cx, cy, huber, min_diag, max_diag, radius0;
   // ---- hand-over ----
   unsigned* sync;                 // kResSyncBytes of device memory; never reset: epochs grow from launch to launch
@@ -373,7 +375,7 @@ __global__ __launch_bounds__(kResThreads) void k_resident(ResidentParams P) {
       SolveParams so{};
       so.packed = P.packed; so.cams = P.cams[cur]; so.cams_cand = P.cams[1 - cur]; so.delta_c = s_dc; so.sc = P.sc; so.scal = P.scal;
       so.geom = P.geom[cur]; so.geom_cand = final_pass ? nullptr : s_gc; so.tab = P.tab;
-      so.n_frames = P.n_frames; so.n_free = P.n_free; so.n_pairs = P.n_pairs; so.stride = P.part_stride; so.fixed_slot = P.fixed_slot;
+      so.n_frames = P.n_frames; so.n_free = P.n_free; so.n_pairs = P.n_pairs; so.stride = P.part_stride; so.anchor_mask = P.anchor_mask;
       so.init_scale = init_scale; so.jacobi = P.jacobi; so.radius = radius; so.min_diag = P.min_diag; so.max_diag = P.max_diag;
       so.final_pass = final_pass;
       solve_blocked<true, kSolveBlockedThreads>(so, reinterpret_cast<double*>(pool), tid);

@@ -184,7 +184,8 @@ struct SolveParams {
   CamGeom* geom_cand;       // candidate geometry output (null: produced elsewhere)
   const uint32_t* tab;      // window-shape tables built by the host at pba_set_cameras (solve_tables): [TRI] row << 16 | column of the
                             // packed triangle entries, then the update work items row | block column << 16
-  int32_t n_frames, n_free, n_pairs, stride, fixed_slot;
+  int32_t n_frames, n_free, n_pairs, stride;
+  uint32_t anchor_mask;     // constant slots (pba_slot_rule.h)
   int32_t init_scale, jacobi;
   double radius, min_diag, max_diag;
   // asynchronous driver
@@ -288,7 +289,7 @@ __device__ __forceinline__ void solve_epilogue(const SolveParams& p, int n, cons
       double cam6[6];
       const int fa = p.geom[c].free_index;
       for (int k = 0; k < 6; ++k) cam6[k] = p.cams[6 * c + k] + (fa >= 0 ? -sc[6 * fa + k] * y[6 * fa + k] : 0.0);
-      cam_geom_one(cam6 - 6 * c, p.geom_cand, c, p.fixed_slot);
+      cam_geom_one(cam6 - 6 * c, p.geom_cand, c, p.anchor_mask);
     }
   }
   if (tid < 64) {
@@ -438,13 +439,13 @@ __device__ inline void cam_geom_scalar(const double cam6[6], double* cg) {
 // 32 lanes per camera (sub = lane within the group, the group aligned to 32 lanes of a wave): B = (w w^T + (R^T - I) [w]x) /
 // theta^2 by lanes 0..8, dR_k = R [B_k]x by lanes 0..26 (three cross-lane reads of B's column k), everything stored.
 // Same formulas and operand order as cam_geom_one.
-__device__ inline void cam_geom_finish(const double* cg, CamGeom* __restrict__ out, int c, int fixed_slot, int sub) {
+__device__ inline void cam_geom_finish(const double* cg, CamGeom* __restrict__ out, int c, uint32_t anchor_mask, int sub) {
   CamGeom& g = out[c];
   const bool rod = cg[21] != 0.0;
   if (sub < 3) { g.aa[sub] = cg[sub]; g.t[sub] = cg[3 + sub]; g.w[sub] = cg[6 + sub]; }
   if (sub == 3) {
-    g.rodrigues = rod; g.is_free = (c != fixed_slot);
-    g.free_index = (c == fixed_slot) ? -1 : (fixed_slot >= 0 && c > fixed_slot ? c - 1 : c);
+    g.rodrigues = rod; g.is_free = slot_is_free(anchor_mask, c);
+    g.free_index = slot_free_index(anchor_mask, c);
     g.pad = 0;
   }
   if (sub == 4) { g.ct = cg[9]; g.st = cg[10]; }
@@ -841,7 +842,7 @@ __device__ __forceinline__ void solve_blocked(SolveParams& p, double* smem, int 
   PBA_TS(6);
   if (p.geom_cand) {
     __syncthreads();
-    for (int c = tid / 32; c < p.n_frames; c += T / 32) cam_geom_finish(s_cg[c], p.geom_cand, c, p.fixed_slot, tid & 31);
+    for (int c = tid / 32; c < p.n_frames; c += T / 32) cam_geom_finish(s_cg[c], p.geom_cand, c, p.anchor_mask, tid & 31);
   }
   PBA_TS(5);
   if (PBA_PHASE_TIMING && p.dbg && tid == 0)

@@ -175,11 +175,24 @@ class Engine:
                                             _ptr(os_), _ptr(w)), "pba_set_problem")
         self.n_points, self.n_obs = xyz.shape[0], op.shape[0]
 
-    def set_cameras(self, cams, fixed_slot=0):
+    def set_cameras(self, cams, fixed_slot=0, constant_slots=None):
+        """cams [n_frames, 6].  fixed_slot: the one constant camera (-1: none).  constant_slots: an iterable of slots held constant
+        (anchor frames, pba_set_cameras_anchored); it overrides fixed_slot."""
         cams = np.ascontiguousarray(cams, np.float64)
-        self._check(self._L.pba_set_cameras(self._h, _ptr(cams), cams.shape[0], int(fixed_slot)), "pba_set_cameras")
+        if constant_slots is None:
+            self._check(self._L.pba_set_cameras(self._h, _ptr(cams), cams.shape[0], int(fixed_slot)), "pba_set_cameras")
+            n_const = 1 if fixed_slot >= 0 else 0
+        else:
+            slots = sorted({int(s) for s in constant_slots})
+            if any(s < 0 or s >= 32 for s in slots):
+                raise ValueError("constant_slots: slots are 0..31, got %r" % (slots,))
+            mask = 0
+            for s in slots:
+                mask |= 1 << s
+            self._check(self._L.pba_set_cameras_anchored(self._h, _ptr(cams), cams.shape[0], mask), "pba_set_cameras_anchored")
+            n_const = len(slots)
         self.n_frames = cams.shape[0]
-        self.n_free = self.n_frames - (1 if fixed_slot >= 0 else 0)
+        self.n_free = self.n_frames - n_const
 
     def load(self, prob):
         """Uploads a WindowProblem (frames from prob.images)."""

@@ -169,7 +169,8 @@ PhotometricBundleAdjustment::Options::Options(const utils::ConfigFile& cf)
       numThreads(cf.get<int>("numThreads", -1)),
       verbose((bool)cf.get<int>("verbose", 1)),
       device(cf.get<int>("device", 0)),
-      camerasConstant((bool)cf.get<int>("camerasConstant", 0)) {}
+      camerasConstant((bool)cf.get<int>("camerasConstant", 0)),
+      numConstantFrames(cf.get<int>("numConstantFrames", 1)) {}
 
 std::ostream& operator<<(std::ostream& os, const PhotometricBundleAdjustment::Options& o) {
   using DT = PhotometricBundleAdjustment::Options::DescriptorType;
@@ -179,7 +180,7 @@ std::ostream& operator<<(std::ostream& os, const PhotometricBundleAdjustment::Op
      << "\nmaxValidDepth = " << o.maxValidDepth << "\nslidingWindowSize = " << o.slidingWindowSize << "\npatchRadius = " << o.patchRadius
      << "\ndoGaussianWeighting = " << (o.doGaussianWeighting ? 1 : 0) << "\nrobustThreshold = " << o.robustThreshold
      << "\ndescriptorType = " << dt << "\nnumThreads = " << o.numThreads << "\nverbose = " << (o.verbose ? 1 : 0) << "\ndevice = " << o.device
-     << "\ncamerasConstant = " << (o.camerasConstant ? 1 : 0) << "\n";
+     << "\ncamerasConstant = " << (o.camerasConstant ? 1 : 0) << "\nnumConstantFrames = " << o.numConstantFrames << "\n";
   return os;
 }
 
@@ -262,6 +263,9 @@ PhotometricBundleAdjustment::PhotometricBundleAdjustment(const Calibration& cali
 PhotometricBundleAdjustment::PhotometricBundleAdjustment(const Calibration& calib, const ImageSize& image_size,
                                                          const Options& options)
     : _calib(calib), _image_size(image_size), _options_ptr(new Options(options)) {
+  if (options.numConstantFrames < 1 || options.numConstantFrames > options.slidingWindowSize - 1)
+    throw std::invalid_argument("numConstantFrames = " + std::to_string(options.numConstantFrames) + " is outside 1 .. slidingWindowSize - 1 = " +
+                                std::to_string(options.slidingWindowSize - 1) + ": at least one frame of the window must stay free");
   // Multi-channel descriptor types: the reference's debug builds stop at `assert(p0.size() == w.size())`
   // (photobundle.cc:684: C P descriptor entries against P patch weights); its release builds run, with the weights
   // restarting per channel (:714-721), and that is what is built here.
@@ -620,6 +624,7 @@ struct PhotometricBundleAdjustment::OptimizeState {
   double t_o[6] = {0, 0, 0, 0, 0, 0};
   double t_lo = 0.0;
   uint32_t frame_id_start = 0, frame_id_end = 0;
+  int n_anchored = 0;      // oldest frames held constant through pba_set_cameras_anchored (0: the one-slot call, as ever)
   std::vector<double> cams, xyz;
   std::vector<ScenePoint*> selected;
   pba_solver_options so;
@@ -720,7 +725,16 @@ bool PhotometricBundleAdjustment::optimizeAssemble(OptimizeState& st) {
     const int32_t first_slot = (int32_t)(frame_id_start % window);
     const bool first_in_bundle = std::find(obs_slot.begin(), obs_slot.end(), first_slot) != obs_slot.end();
     if (!first_in_bundle) std::fprintf(stderr, "first camera is not in bundle\n");
-    check(_engine, pba_set_cameras(_engine, cams.data(), window, first_slot), "pba_set_cameras");
+    // anchor frames: the oldest frames of the window, one of them as ever unless Options::numConstantFrames asks for more
+    const int n_const = std::min(_options_ptr->numConstantFrames, (int)(frame_id_end - frame_id_start));
+    if (n_const <= 1) {
+      check(_engine, pba_set_cameras(_engine, cams.data(), window, first_slot), "pba_set_cameras");
+    } else {
+      uint32_t anchor_mask = 0;
+      for (int k = 0; k < n_const; ++k) anchor_mask |= 1u << ((frame_id_start + (uint32_t)k) % (uint32_t)window);
+      check(_engine, pba_set_cameras_anchored(_engine, cams.data(), window, anchor_mask), "pba_set_cameras_anchored");
+      st.n_anchored = n_const;
+    }
     if (_options_ptr->camerasConstant) check(_engine, pba_set_cameras_constant(_engine, 1), "pba_set_cameras_constant");
     st.lap(2);
     pba_default_solver_options(&st.so);     // GetSolverOptions (:738-761)
@@ -754,7 +768,8 @@ void PhotometricBundleAdjustment::optimizeFinish(OptimizeState& st, Result* resu
     for (size_t i = 0; i < selected.size(); ++i) for (int k = 0; k < 3; ++k) selected[i]->X[k] = xyz[3 * i + k];
     // put back the refined camera poses (:841-844)
     if (!cams_const) {
-      for (uint32_t id = frame_id_start; id <= frame_id_end; ++id)
+      // (anchor frames did not move: their poses stay as they are -- no parameter round trip)
+      for (uint32_t id = frame_id_start + (uint32_t)st.n_anchored; id <= frame_id_end; ++id)
         _trajectory.atId((int)id) = ParamsToPose(&cams[6 * (id % window)]).inverse();
     }
   }

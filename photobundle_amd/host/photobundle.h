@@ -123,6 +123,10 @@ class PhotometricBundleAdjustment {
     // structure-only refinement (new): every camera is a constant parameter block (pba_set_cameras_constant), the optimisation
     // refines the scene points against the trajectory exactly as the inputs chained it
     bool camerasConstant = false;
+    // anchor frames (new): optimize() holds the min(numConstantFrames, frames in the window - 1) OLDEST frames of the window constant
+    // (pba_set_cameras_anchored).  1 is the reference's behaviour (:809-813); valid values are 1 .. slidingWindowSize - 1, anything
+    // else throws std::invalid_argument when the class is constructed.  trackFrame is not affected.
+    int numConstantFrames = 1;
 
     Options() {}
     Options(const utils::ConfigFile& cf);
