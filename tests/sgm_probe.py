@@ -2,12 +2,11 @@
 not collected."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "photobundle_amd")
+from host_class_probe import build
+
 INT_KEYS = ("numberOfDisparities", "sobelCapValue", "censusRadius", "windowRadius", "smoothnessPenaltySmall",
             "smoothnessPenaltyLarge", "consistencyThreshold")
 FLOAT_KEYS = ("disparityFactor", "censusWeightFactor")
@@ -19,11 +18,7 @@ def _ptr(a):
 
 class SgmHostProbe:
     def __init__(self, out_dir):
-        so = os.path.join(str(out_dir), "libsgm_host_probe.so")
-        subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so,
-                               os.path.join(ROOT, "tests", "sgm_host_probe.cpp"), "-L" + PKG, "-lphotobundle", "-lpba_hip",
-                               "-Wl,-rpath," + PKG])
-        self.L = C.CDLL(so)
+        self.L = C.CDLL(build("sgm_host_probe.cpp", out_dir, openmp=False))
 
     def parse(self, cfg_text, tmp_dir):
         """-> (dict of the nine keys, whether StereoAlgorithm selects SGM); RuntimeError with the message on a refusal."""

@@ -2,12 +2,11 @@
 caller owns.  Test helper, not collected."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "photobundle_amd")
+from host_class_probe import build
+
 PARAM_FIELDS = ("pre_filter_type", "pre_filter_size", "pre_filter_cap", "sad_window_size", "min_disparity",
                 "number_of_disparities", "texture_threshold", "uniqueness_ratio", "speckle_window_size", "speckle_range",
                 "try_smaller_windows", "disp12_max_diff")
@@ -19,11 +18,7 @@ def _ptr(a):
 
 class HostProbe:
     def __init__(self, out_dir):
-        so = os.path.join(str(out_dir), "libstereo_host_probe.so")
-        subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so,
-                               os.path.join(ROOT, "tests", "stereo_host_probe.cpp"), "-L" + PKG, "-lphotobundle", "-lpba_hip",
-                               "-Wl,-rpath," + PKG])
-        self.L = C.CDLL(so)
+        self.L = C.CDLL(build("stereo_host_probe.cpp", out_dir, openmp=False))
 
     def parse(self, cfg_text, tmp_dir):
         path = os.path.join(str(tmp_dir), "stereo_probe.cfg")

@@ -1,4 +1,4 @@
-"""Anchor frames (pba_set_cameras_anchored) without a device: the numpy yardstick tests/anchors_ref.py against the oracle's own solver
+"""Anchor frames (pba_set_cameras_anchored) without a device: the numpy yardstick tests/lm_yardstick.py (Dense) against the oracle's own solver
 (one constant slot) and against scipy.optimize.least_squares (two and three), the qualification of the device trace cases on the
 yardstick alone, the slot rule of photobundle_amd/csrc/pba_slot_rule.h compiled stand-alone, and the ABI / Python / host plumbing."""
 import os
@@ -10,7 +10,8 @@ import pytest
 from oracle import oracle
 from photobundle_amd import synthetic
 
-import anchors_ref as ref
+import anchors_cases as cases
+import lm_yardstick as lm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -27,7 +28,7 @@ def test_one_slot_set_reproduces_the_oracle_trace(fixed_slot, huber):
     p.fixed_slot = fixed_slot
     n_it = 12
     res_o = oracle.solve(p, oracle.default_options(max_num_iterations=n_it))
-    res = ref.solve(p, (fixed_slot,), max_num_iterations=n_it)
+    res = lm.Dense(p, (fixed_slot,)).solve(max_num_iterations=n_it)
     its, log = res_o["iterations"], res["iterations"]
     kind = next(k for k in KINDS if res["message"].startswith(k))
     assert res_o["message"].startswith(kind), (res["message"], res_o["message"])
@@ -50,7 +51,7 @@ def test_first_step_reduced_system_equals_the_dense_reference_step():
     """first_step()'s Schur elimination against tests/gpu_util.py's reference_step (dense Jacobian from per-block rows), one slot."""
     from gpu_util import dense_system, reference_step
     p = synthetic.make_window(n_frames=3, n_points=40, radius=1, size=(96, 128), K=(160.0, 160.0, 64.0, 48.0), huber=0.05, seed_offset=1)
-    st = ref.first_step(p, (p.fixed_slot,))
+    st = lm.Dense(p, (p.fixed_slot,)).first_step()
     J, r, n_cam = dense_system(p)
     rs = reference_step(J, r, n_cam, 1e4)
     assert n_cam == st["n_cam"]
@@ -74,11 +75,11 @@ def test_end_point_matches_scipy_least_squares_over_the_free_columns(n_frames, s
     p = synthetic.make_window(n_frames=n_frames, n_points=60, radius=1, size=(96, 128), K=(160.0, 160.0, 64.0, 48.0),
                               rot_deg=0.05, trans=0.01, depth_noise=0.005, seed_offset=seed)
     rs = _Restatement(p)
-    rs.free = ref.free_slots(p, slots)                    # the restatement's camera columns: the slots outside the set
+    rs.free = lm.free_slots(p, slots)                    # the restatement's camera columns: the slots outside the set
     rs.col = {s: 6 * k for k, s in enumerate(rs.free)}
     rs.n_cam = 6 * len(rs.free)
     theta0 = rs.pack(p.cams, p.xyz)
-    res = ref.solve(p, slots, max_num_iterations=400, function_tolerance=1e-14, gradient_tolerance=1e-14, parameter_tolerance=1e-14)
+    res = lm.Dense(p, slots).solve(max_num_iterations=400, function_tolerance=1e-14, gradient_tolerance=1e-14, parameter_tolerance=1e-14)
     sp = least_squares(rs.residuals, theta0, jac=rs.jacobian, method="trf", x_scale="jac", ftol=1e-15, xtol=1e-15, gtol=1e-15,
                        max_nfev=2000)
     print("anchors %s: start %.6e  yardstick %.6e  scipy %.6e" % (slots, res["initial_cost"], res["final_cost"], sp.cost))
@@ -97,25 +98,25 @@ def test_end_point_matches_scipy_least_squares_over_the_free_columns(n_frames, s
 def trace_runs():
     """The yardstick on every trace case, on autodiff evaluations: (problem, slots, extras, rays, rho, result, compared iterations)."""
     out = {}
-    for name in ref.TRACE_CASES:
-        p, slots, extras, rays, rho = ref.trace_case(name)
-        res = ref.solve(p, slots, rays, rho, max_num_iterations=ref.REF_ITERATIONS)
-        out[name] = (p, slots, extras, rays, rho, res, ref.compared_iterations(res))
+    for name in cases.TRACE_CASES:
+        p, slots, extras, rays, rho = cases.trace_case(name)
+        res = lm.Dense(p, slots, rays, rho).solve(max_num_iterations=cases.REF_ITERATIONS)
+        out[name] = (p, slots, extras, rays, rho, res, lm.compared_iterations(res))
     return out
 
 
-@pytest.mark.parametrize("name", sorted(ref.TRACE_CASES))
+@pytest.mark.parametrize("name", sorted(cases.TRACE_CASES))
 def test_trace_cases_have_four_clear_iterations(trace_runs, name):
     res, n_cmp = trace_runs[name][5:]
     assert n_cmp >= 4, [(i["step_is_successful"], i["relative_decrease"]) for i in res["iterations"]]
 
 
-@pytest.mark.parametrize("name", sorted(ref.TRACE_CASES))
+@pytest.mark.parametrize("name", sorted(cases.TRACE_CASES))
 def test_trace_cases_qualify(trace_runs, name):
     """As test_points_only_cpu.py qualifies its cases: run on analytic evaluations the yardstick takes the same decisions and ends the
     compared iterations within 1e-6 of the run on autodiff evaluations, in the parameters the program optimises."""
     p, slots, extras, rays, rho, res, n_cmp = trace_runs[name]
-    ana = ref.solve(p, slots, rays, rho, autodiff=False, max_num_iterations=n_cmp - 1)
+    ana = lm.Dense(p, slots, rays, rho, autodiff=False).solve(max_num_iterations=n_cmp - 1)
     a, b = res["iterations"][:n_cmp], ana["iterations"]
     assert len(b) == n_cmp
     assert [i["step_is_successful"] for i in a] == [i["step_is_successful"] for i in b]
@@ -124,7 +125,7 @@ def test_trace_cases_qualify(trace_runs, name):
     cams_a, x_a = res["states"][n_cmp - 1]
     diff = max(np.abs(cams_a - ana["cams"]).max(), np.abs(x_a - ana["x"]).max())
     print(name, "autodiff against analytic after %d iterations: %.3e" % (n_cmp - 1, diff))
-    assert diff <= ref.QUALIFY_BAR
+    assert diff <= cases.QUALIFY_BAR
     for s in slots:
         assert np.array_equal(res["cams"][s], p.cams[s])
     if rays is not None:      # every evaluated candidate stays inside the domain of the parameterisation (inverse depths > 0)
@@ -134,11 +135,11 @@ def test_trace_cases_qualify(trace_runs, name):
 def test_traces_hold_both_kinds_of_decision():
     """From the default radius the four windows accept and reject: the device traces are compared on both kinds."""
     kinds = set()
-    for name in sorted(ref.TRACE_CASES):
-        p, slots, extras, rays, rho = ref.trace_case(name)
+    for name in sorted(cases.TRACE_CASES):
+        p, slots, extras, rays, rho = cases.trace_case(name)
         if rays is not None:
             continue
-        res = ref.solve(p, slots, max_num_iterations=40)
+        res = lm.Dense(p, slots).solve(max_num_iterations=40)
         its = res["iterations"][1:]
         print(name, "log entries %d, rejected %d (%s)" % (len(res["iterations"]), sum(not i["step_is_successful"] for i in its), res["message"]))
         kinds |= {bool(i["step_is_successful"]) for i in its}
@@ -148,10 +149,11 @@ def test_traces_hold_both_kinds_of_decision():
 def test_two_anchors_close_the_gauge():
     """The undamped reduced camera system: singular with one constant slot (the scale of the window is free), well conditioned with
     two -- the table of DESIGN.md, on the 3 x 40 dense window."""
-    p, _, _, _, _ = ref.trace_case("3x40-dense-r1-anchors-0-2")
+    p, _, _, _, _ = cases.trace_case("3x40-dense-r1-anchors-0-2")
 
     def cond(slots):
-        H, g, n_cam = ref.normal_equations(p, slots, np.array(p.cams), np.array(p.xyz))
+        prog = lm.Dense(p, slots)
+        H, n_cam = prog.linearize((np.array(p.cams), np.array(p.xyz)))["H"], prog.n_cam
         S = H[:n_cam, :n_cam] - H[:n_cam, n_cam:] @ np.linalg.solve(H[n_cam:, n_cam:], H[n_cam:, :n_cam])
         w = np.linalg.eigvalsh(0.5 * (S + S.T))
         return abs(w).max() / max(abs(w).min(), 1e-300)
@@ -161,14 +163,21 @@ def test_two_anchors_close_the_gauge():
     assert c1 > 1e10 and c2 < 1e7
 
 
+def _pose_costs(p, slots):
+    """Pose-only mode: (cost of the anchored cameras' residual blocks, cost of the program = every other block, number of program
+    blocks)."""
+    st = lm.CameraBlocks(p, slots).first_step()
+    return st["fixed_cost"], st["cost"], st["num_residual_blocks"]
+
+
 def test_pose_only_fixed_cost_sums_the_anchored_blocks():
     p = synthetic.make_window(n_frames=5, n_points=60, radius=1, size=(96, 128), K=(160.0, 160.0, 64.0, 48.0), huber=0.05)
-    fixed, prog, n_prog = ref.pose_fixed_cost(p, (0, 3))
+    fixed, prog, n_prog = _pose_costs(p, (0, 3))
     total = oracle.cost(p)[0]
     assert np.isclose(fixed + prog, total, rtol=1e-13)
     assert n_prog == int(np.sum((p.obs_slot != 0) & (p.obs_slot != 3)))
-    f0, _, _ = ref.pose_fixed_cost(p, (0,))
-    f3, _, _ = ref.pose_fixed_cost(p, (3,))
+    f0, _, _ = _pose_costs(p, (0,))
+    f3, _, _ = _pose_costs(p, (3,))
     assert fixed == f0 + f3
 
 
@@ -243,17 +252,17 @@ def test_python_wrapper_takes_constant_slots():
 
 
 def test_class_header_has_the_option(tmp_path):
-    import anchors_probe
+    import host_class_probe
     with open(os.path.join(ROOT, "photobundle_amd", "host", "photobundle.h")) as f:
         assert "int numConstantFrames = 1;" in f.read()
-    probe = anchors_probe.AnchorsProbe(tmp_path)
-    assert probe.default() == 1
-    assert "numConstantFrames = 3\n" in probe.print_options(3)
+    probe = host_class_probe.HostClassProbe(tmp_path)
+    assert probe.default_num_constant() == 1
+    assert "numConstantFrames = 3\n" in probe.print_options(num_constant=3)
     # outside 1 .. slidingWindowSize - 1: refused when the class is constructed, before a device is asked for
     for levels in (1, 2):
         for k in (0, 5, 7):
             with pytest.raises(RuntimeError, match="numConstantFrames = %d is outside 1 .. slidingWindowSize - 1 = 4" % k):
-                probe.create((32, 48), (50.0, 50.0, 24.0, 16.0), window=5, radius=1, num_constant=k, levels=levels)
+                probe.create(levels, (32, 48), (50.0, 50.0, 24.0, 16.0), window=5, radius=1, num_constant=k)
 
 
 def _run_kitti(args):
@@ -264,9 +273,9 @@ def _run_kitti(args):
 
 
 def _tiny_sequence(tmp, extra):
-    import track_probe
+    import host_class_probe
     img = np.zeros((32, 48), np.uint8)
-    track_probe.write_sequence(str(tmp), [img], [np.ones((32, 48), np.float32)], (50.0, 50.0, 24.0, 16.0), [np.eye(4)])
+    host_class_probe.write_sequence(str(tmp), [img], [np.ones((32, 48), np.float32)], (50.0, 50.0, 24.0, 16.0), [np.eye(4)])
     cfg = os.path.join(str(tmp), "test.cfg")
     with open(cfg, "w") as f:
         f.write("DataDirectory = %s\nTrajectory = %s/init.txt\nverbose = 0\nslidingWindowSize = 4\n%s" % (tmp, tmp, extra))

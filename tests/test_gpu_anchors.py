@@ -1,4 +1,4 @@
-"""-m gpu: anchor frames (pba_set_cameras_anchored) against the numpy yardstick tests/anchors_ref.py, which evaluates through the
+"""-m gpu: anchor frames (pba_set_cameras_anchored) against the numpy yardstick tests/lm_yardstick.py (Dense), which evaluates through the
 unchanged oracle.
 
 Tolerances are the project's own, as tests/test_gpu_points_only.py and tests/test_gpu_pose_only.py hold them: system entries 1e-9 of the
@@ -15,7 +15,8 @@ import pytest
 from photobundle_amd import synthetic
 from photobundle_amd.engine import Engine, EngineError, default_solver_options, solve_batch
 
-import anchors_ref as ref
+import anchors_cases as cases
+import lm_yardstick as lm
 
 pytestmark = pytest.mark.gpu
 
@@ -63,15 +64,15 @@ def _strip(res):
 
 @functools.lru_cache(maxsize=None)
 def _case(name):
-    return ref.trace_case(name)
+    return cases.trace_case(name)
 
 
 @functools.lru_cache(maxsize=None)
 def _yardstick(name):
     """The yardstick's run of a trace case, computed once and shared: (result, compared iterations)."""
     p, slots, _, rays, rho = _case(name)
-    res = ref.solve(p, slots, rays, rho, max_num_iterations=ref.REF_ITERATIONS)
-    return res, ref.compared_iterations(res)
+    res = lm.Dense(p, slots, rays, rho).solve(max_num_iterations=cases.REF_ITERATIONS)
+    return res, lm.compared_iterations(res)
 
 
 @functools.lru_cache(maxsize=None)
@@ -100,7 +101,7 @@ def test_fixed_slot_call_equals_the_one_bit_mask(driver):
 
 # ---- 2. the reduced system of the first step -----------------------------------------------------------------------------------------
 def _check_system(p, slots, tag):
-    st = ref.first_step(p, slots, radius=1e4)
+    st = lm.Dense(p, slots).first_step(radius=1e4)
     with _engine(p, slots=slots) as e:
         assert e.n_free == len(st["free"])
         e.linearize()
@@ -170,7 +171,7 @@ def test_free_camera_without_a_residual_block():
     p.obs_point, p.obs_slot = p.obs_point[keep], p.obs_slot[keep]
     assert len(np.unique(p.obs_point)) == p.n_points
     st, _ = _check_system(p, (0, 4), "free camera 2 without residual blocks")
-    assert ref.live_cameras(p, (0, 4)) == [1, 3] and st["free"] == [1, 2, 3]
+    assert lm.Dense(p, (0, 4)).live == [1, 3] and st["free"] == [1, 2, 3]
     assert not st["delta_c"][1].any()
 
 
@@ -196,7 +197,7 @@ def _check_trace(name, res, res_ref, n_cmp, p, slots):
     assert np.isclose(res["initial_cost"], res_ref["initial_cost"], rtol=1e-9)
 
 
-TRACES = [n for n in sorted(ref.TRACE_CASES) if "inverse-depth" not in ref.TRACE_CASES[n][2]]
+TRACES = [n for n in sorted(cases.TRACE_CASES) if "inverse-depth" not in cases.TRACE_CASES[n][2]]
 
 
 @pytest.mark.parametrize("driver", ["default", "host-stepped"])
@@ -243,7 +244,7 @@ def test_resident_pipelined_and_batched_give_identical_bits(name):
 
 # ---- 4. the narrow / wide boundary --------------------------------------------------------------------------------------------------
 def test_sixteen_slots_with_two_anchors_run_the_narrow_kernels():
-    p = ref.boundary_window(16)
+    p = cases.boundary_window(16)
     slots = (0, 1)
     st, _ = _check_system(p, slots, "16 slots, 2 anchors")
     assert st["n_cam"] == 6 * 14
@@ -252,15 +253,15 @@ def test_sixteen_slots_with_two_anchors_run_the_narrow_kernels():
         assert e.solve_driver() in ("resident", "pipelined")      # not the host-stepped driver of the wide chain
 
 
-@pytest.mark.parametrize("name", sorted(ref.BOUNDARY_WIDE))
+@pytest.mark.parametrize("name", sorted(cases.BOUNDARY_WIDE))
 def test_wide_chain_with_anchors(name):
-    n_frames, slots = ref.BOUNDARY_WIDE[name]
-    p = ref.boundary_window(n_frames)
+    n_frames, slots = cases.BOUNDARY_WIDE[name]
+    p = cases.boundary_window(n_frames)
     assert p.n_points == 64
     st, _ = _check_system(p, slots, name)
     assert st["n_cam"] == 6 * (n_frames - len(slots))
-    res_ref = ref.solve(p, slots, max_num_iterations=6)
-    n_cmp = min(ref.compared_iterations(res_ref), 5)
+    res_ref = lm.Dense(p, slots).solve(max_num_iterations=6)
+    n_cmp = min(lm.compared_iterations(res_ref), 5)
     assert n_cmp >= 3
     with _engine(p, slots=slots, keep=False) as e:
         res = e.solve(default_solver_options(max_num_iterations=n_cmp - 1))
@@ -275,16 +276,11 @@ def test_wide_chain_with_anchors(name):
 
 # ---- 5. the constant modes under a mask -----------------------------------------------------------------------------------------------
 def test_pose_only_with_two_anchors():
-    import pose_only_ref
-    from oracle import oracle
     p = _window5()
     slots = (0, 3)
-    fixed_ref, prog_ref, n_prog = ref.pose_fixed_cost(p, slots)
-    lin = oracle.linearize(p)
-    cols = [1, 2, 4]
-    U, g = lin["U"][cols], lin["grad_cams"][cols]
-    scale = 1.0 / (1.0 + np.sqrt(np.einsum("kii->ki", U)))
-    st = pose_only_ref._step(U, g, scale, 1e4, 1e-6, 1e32)
+    st = lm.CameraBlocks(p, slots).first_step(radius=1e4)
+    assert st["cols"] == [1, 2, 4]
+    fixed_ref, prog_ref, n_prog = st["fixed_cost"], st["cost"], st["num_residual_blocks"]
     with _engine(p, slots=slots) as e:
         e.set_points_constant()
         e.linearize()
@@ -397,7 +393,7 @@ def test_refusals():
         e.set_cameras(p.cams, constant_slots=(4,))
         assert e.solve(o)["final_cost"] > 0.0
     # a wide window keeps the wide refusals: inverse depths on 17 slots, however few cameras are free
-    pw = ref.boundary_window(17)
+    pw = cases.boundary_window(17)
     rays, rho = synthetic.inverse_depth_rays(pw)
     with _engine(pw, slots=range(16), keep=False) as e:
         with pytest.raises(EngineError, match="invalid argument.*inverse-depth mode is not built for wide windows"):
@@ -414,8 +410,8 @@ SEQ_SIZE, SEQ_K = (120, 160), (200.0, 200.0, 80.0, 60.0)
 
 def _sequence(n):
     """The synthetic sequence of tests/test_gpu_points_only.py: exactly photo-consistent frames, depth maps scaled by a smooth +-2 % field."""
-    import track_probe
-    imgs, depths, T_gt, local = track_probe.sequence(n, SEQ_SIZE, SEQ_K)
+    import host_class_probe
+    imgs, depths, T_gt, local = host_class_probe.sequence(n, SEQ_SIZE, SEQ_K)
     rows, cols = depths[0].shape
     y, x = np.mgrid[0:rows, 0:cols]
     field = 1.0 + 0.02 * np.sin(2 * np.pi * x / cols) * np.cos(2 * np.pi * y / rows)
@@ -423,13 +419,13 @@ def _sequence(n):
 
 
 def test_host_class_leaves_the_anchor_frames_alone(tmp_path):
-    import anchors_probe
+    import host_class_probe
     n, window = 8, 4
     imgs, depths, local = _sequence(n)
-    probe = anchors_probe.AnchorsProbe(tmp_path)
+    probe = host_class_probe.HostClassProbe(tmp_path)
     runs = {}
     for key in (2, 1, None):
-        probe.create(SEQ_SIZE, SEQ_K, window=window, radius=1, min_score=0.65, num_constant=key)
+        probe.create(1, SEQ_SIZE, SEQ_K, window=window, radius=1, min_score=0.65, num_constant=key)
         out = [(i, probe.add(imgs[i], depths[i], local[i])) for i in range(n)]
         runs[key] = [(i, r) for i, r in out if r is not None]
         assert len(runs[key]) == n - (window - 1)
@@ -452,8 +448,8 @@ def test_host_class_leaves_the_anchor_frames_alone(tmp_path):
 
 
 def test_run_kitti_runs_with_the_key(tmp_path):
-    import track_probe
-    run = os.path.join(track_probe.PKG, "bin", "run_kitti")
+    import host_class_probe
+    run = os.path.join(host_class_probe.PKG, "bin", "run_kitti")
     n_frames = 8
     imgs, depths, local = _sequence(n_frames)
     common = "maxNumPoints = 4096\nslidingWindowSize = 4\npatchRadius = 1\nminScore = 0.65\nrobustThreshold = 0.05\nverbose = 0\n"
@@ -461,7 +457,7 @@ def test_run_kitti_runs_with_the_key(tmp_path):
     def prepare(name, extra):
         d = os.path.join(str(tmp_path), name)
         os.makedirs(d)
-        track_probe.write_sequence(d, imgs, depths, SEQ_K, local)
+        host_class_probe.write_sequence(d, imgs, depths, SEQ_K, local)
         cfg = os.path.join(d, "test.cfg")
         with open(cfg, "w") as f:
             f.write("DataDirectory = %s\nTrajectory = %s/init.txt\n%s%s" % (d, d, common, extra))

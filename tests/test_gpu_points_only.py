@@ -1,4 +1,4 @@
-"""-m gpu: structure-only solves (pba_set_cameras_constant) against the numpy yardstick tests/points_only_ref.py, which evaluates through
+"""-m gpu: structure-only solves (pba_set_cameras_constant) against the numpy yardstick tests/lm_yardstick.py (PointBlocks), which evaluates through
 the unchanged oracle.
 
 Tolerances are the project's own, as tests/test_gpu_pose_only.py holds them: the system blocks 1e-9 of the largest entry, the trace
@@ -13,7 +13,8 @@ import pytest
 from photobundle_amd import synthetic
 from photobundle_amd.engine import Engine, EngineError, default_solver_options, solve_batch
 
-import points_only_ref as ref
+import lm_yardstick as lm
+import points_only_cases as cases
 from gpu_util import make_engine
 
 pytestmark = pytest.mark.gpu
@@ -23,20 +24,20 @@ TIME_FIELDS = ("iteration_time_in_seconds", "step_solver_time_in_seconds", "cumu
 
 @functools.lru_cache(maxsize=None)
 def _case(name):
-    return ref.trace_case(name)
+    return cases.trace_case(name)
 
 
 @functools.lru_cache(maxsize=None)
 def _yardstick(name):
     """The yardstick's run of a trace case, computed once and shared: (result, compared iterations)."""
     p, _, rays, rho = _case(name)
-    res = ref.solve(p, rays, rho, max_num_iterations=ref.REF_ITERATIONS)
-    return res, ref.compared_iterations(res)
+    res = lm.PointBlocks(p, rays, rho).solve(max_num_iterations=cases.REF_ITERATIONS)
+    return res, lm.compared_iterations(res)
 
 
 @functools.lru_cache(maxsize=None)
 def _boundary_window():
-    return ref.cameras_to_ground_truth(synthetic.make_window(**ref.BOUNDARY_WINDOW))
+    return cases.cameras_to_ground_truth(synthetic.make_window(**cases.BOUNDARY_WINDOW))
 
 
 def _engine(p, rays=None, rho=None):
@@ -54,7 +55,7 @@ def _check_system(p, e, rays, rho):
         V, rhs = e.point_system()
         with pytest.raises(EngineError, match="no reduced camera system"):
             e.reduced_system()
-    st = ref.first_step(p, radius=1e4, rays=rays, rho=rho)
+    st = lm.PointBlocks(p, rays, rho).first_step(radius=1e4)
     d = st["S"].shape[1]
     V_ref, rhs_ref = np.zeros((p.n_points, 3, 3)), np.zeros((p.n_points, 3))
     V_ref[:, :d, :d], rhs_ref[:, :d] = st["S"], st["rhs"]      # inverse depth: entry 0 of each is set, the rest are zero
@@ -73,22 +74,22 @@ def _check_system(p, e, rays, rho):
     assert np.isclose(info["x_norm"], np.linalg.norm(st["x"]), rtol=1e-13)      # over the points: cameras enter none of the scalars
 
 
-@pytest.mark.parametrize("name", sorted(ref.TRACE_CASES))
+@pytest.mark.parametrize("name", sorted(cases.TRACE_CASES))
 def test_system_matches_the_yardstick(name):
     p, _, rays, rho = _case(name)
     _check_system(p, _engine(p, rays, rho), rays, rho)
 
 
-@pytest.mark.parametrize("k", ref.BOUNDARY_COUNTS)
+@pytest.mark.parametrize("k", cases.BOUNDARY_COUNTS)
 def test_system_at_the_wave_and_workgroup_boundaries(k):
     """The first k points of one 700-point window: one fewer than, exactly and one more than a wave (64) and a workgroup (256) of the
     per-point kernels, one point alone, and three workgroups with a ragged last one."""
-    p = ref.first_points(_boundary_window(), k)
+    p = cases.first_points(_boundary_window(), k)
     assert p.n_points == k
     _check_system(p, _engine(p), None, None)
 
 
-@pytest.mark.parametrize("name", sorted(ref.TRACE_CASES))
+@pytest.mark.parametrize("name", sorted(cases.TRACE_CASES))
 def test_trace_matches_the_yardstick(name):
     p, extras, rays, rho = _case(name)
     res_ref, n_cmp = _yardstick(name)
@@ -153,8 +154,8 @@ def test_rejected_steps_resolve_the_stored_system():
     the decisions, and a re-solve does not rebuild the per-point system: under event profiling the Schur counter counts the launches
     of k_points_system, one per linearisation a step was taken from."""
     p, _, rays, rho = _case("3-frames-r1-huber")
-    res_ref = ref.solve(p, rays, rho, max_num_iterations=6, initial_trust_region_radius=1e12)
-    n_cmp = ref.compared_iterations(res_ref)
+    res_ref = lm.PointBlocks(p, rays, rho).solve(max_num_iterations=6, initial_trust_region_radius=1e12)
+    n_cmp = lm.compared_iterations(res_ref)
     ri = res_ref["iterations"][:n_cmp]
     assert any(i["step_is_valid"] and not i["step_is_successful"] for i in ri[1:])
     with _engine(p, rays, rho) as e:
@@ -178,7 +179,7 @@ def test_a_failed_block_gives_a_zero_step_everywhere():
     of the blocks, so the third pivot of a block is rounding noise and non-positive in many of them (242 of 400 in numpy's Cholesky).
     Some lanes fail, the others have solved: the step must come back as failed and zero EVERYWHERE -- flag, scalars and candidate points."""
     p, _, _, _ = _case("single-observation-5-frames-r1")
-    st = ref.first_step(p, radius=1e30, min_diag=0.0)
+    st = lm.PointBlocks(p).first_step(radius=1e30, min_diag=0.0)
     assert not st["linear_solver_ok"] and not st["delta"].any() and st["model_cost_change"] == 0.0
     o = default_solver_options(min_lm_diagonal=0.0)
     with _engine(p) as e:
@@ -195,7 +196,7 @@ def test_a_failed_block_gives_a_zero_step_everywhere():
     # the driver: five invalid steps in a row end the solve as a failure, the points stay
     with _engine(p) as e:
         res = e.solve(default_solver_options(min_lm_diagonal=0.0, initial_trust_region_radius=1e30, max_trust_region_radius=1e40))
-    res_ref = ref.solve(p, min_lm_diagonal=0.0, initial_trust_region_radius=1e30, max_trust_region_radius=1e40)
+    res_ref = lm.PointBlocks(p).solve(min_lm_diagonal=0.0, initial_trust_region_radius=1e30, max_trust_region_radius=1e40)
     assert [(i["step_is_valid"], i["step_is_successful"]) for i in res["iterations"]] == \
            [(i["step_is_valid"], i["step_is_successful"]) for i in res_ref["iterations"]]
     assert res["termination_type"] == 2 and "invalid steps" in res["message"] and "invalid steps" in res_ref["message"]
@@ -339,15 +340,14 @@ def _chain(local):
 
 
 def test_host_class_refines_the_points_and_leaves_the_poses(tmp_path):
-    import points_probe
-    import track_probe
+    import host_class_probe
     n = 7
-    imgs, depths, T_gt, local = track_probe.sequence(n, SEQ_SIZE, SEQ_K)
+    imgs, depths, T_gt, local = host_class_probe.sequence(n, SEQ_SIZE, SEQ_K)
     depths = _noisy_depths(depths)
-    probe = points_probe.PointsProbe(tmp_path)
+    probe = host_class_probe.HostClassProbe(tmp_path)
     results = {}
     for on in (True, False):
-        probe.create(SEQ_SIZE, SEQ_K, window=4, radius=1, min_score=0.65, cameras_constant=on)
+        probe.create(1, SEQ_SIZE, SEQ_K, window=4, radius=1, min_score=0.65, cameras_constant=on)
         results[on] = [(i, probe.add(imgs[i], depths[i], local[i])) for i in range(n)]
         results[on] = [(i, r) for i, r in results[on] if r is not None]
         assert len(results[on]) == n - 3
@@ -366,17 +366,17 @@ def test_host_class_refines_the_points_and_leaves_the_poses(tmp_path):
 
 @pytest.mark.timeout(900)
 def test_run_kitti_maps_against_the_given_trajectory(tmp_path):
-    import track_probe
-    run = os.path.join(track_probe.PKG, "bin", "run_kitti")
+    import host_class_probe
+    run = os.path.join(host_class_probe.PKG, "bin", "run_kitti")
     n_frames = 8
-    imgs, depths, T_gt, local = track_probe.sequence(n_frames, SEQ_SIZE, SEQ_K)
+    imgs, depths, T_gt, local = host_class_probe.sequence(n_frames, SEQ_SIZE, SEQ_K)
     depths = _noisy_depths(depths)
     common = "maxNumPoints = 4096\nslidingWindowSize = 4\npatchRadius = 1\nminScore = 0.65\nrobustThreshold = 0.05\nverbose = 0\n"
 
     def prepare(name, extra):
         d = os.path.join(str(tmp_path), name)
         os.makedirs(d)
-        track_probe.write_sequence(d, imgs, depths, SEQ_K, local)
+        host_class_probe.write_sequence(d, imgs, depths, SEQ_K, local)
         cfg = os.path.join(d, "test.cfg")
         with open(cfg, "w") as f:
             f.write("DataDirectory = %s\nTrajectory = %s/init.txt\n%s%s" % (d, d, common, extra))

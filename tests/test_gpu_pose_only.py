@@ -1,4 +1,4 @@
-"""-m gpu: pose-only solves (pba_set_points_constant) against the numpy yardstick tests/pose_only_ref.py, which evaluates through the
+"""-m gpu: pose-only solves (pba_set_points_constant) against the numpy yardstick tests/lm_yardstick.py (CameraBlocks), which evaluates through the
 unchanged oracle.
 
 Tolerances are the existing ones: the reduced system as test_gpu_parity.py holds it (1e-9 of the largest entry), the trace as
@@ -11,7 +11,8 @@ from oracle import oracle
 from photobundle_amd import synthetic
 from photobundle_amd.engine import Engine, EngineError, default_solver_options, solve_batch
 
-import pose_only_ref as ref
+import lm_yardstick as lm
+import pose_only_cases as cases
 from gpu_util import make_engine, pose_rmse
 
 pytestmark = pytest.mark.gpu
@@ -20,7 +21,7 @@ TIME_FIELDS = ("iteration_time_in_seconds", "step_solver_time_in_seconds", "cumu
 
 
 def _engine(name):
-    p, extras = ref.trace_case(name)
+    p, extras = cases.trace_case(name)
     e = make_engine(p)
     xyz = None
     if "inverse-depth" in extras:
@@ -47,14 +48,14 @@ def _expected_system(p, st):
     return S, rhs, free
 
 
-@pytest.mark.parametrize("name", sorted(ref.TRACE_CASES))
+@pytest.mark.parametrize("name", sorted(cases.TRACE_CASES))
 def test_system_matches_the_yardstick(name):
     p, e, xyz = _engine(name)
     with e:
         e.linearize()
         info = e.step(1e4, init_scale=True)
         S, rhs = e.reduced_system()
-    st = ref.first_step(p, radius=1e4, xyz=xyz)
+    st = lm.CameraBlocks(p, xyz=xyz).first_step(radius=1e4)
     S_ref, rhs_ref, free = _expected_system(p, st)
     assert S.shape == S_ref.shape
     assert np.abs(S - S_ref).max() <= 1e-9 * np.abs(S_ref).max()
@@ -72,11 +73,11 @@ def test_system_matches_the_yardstick(name):
     assert np.isclose(info["x_norm"], np.linalg.norm(p.cams[st["cols"]]), rtol=1e-13)      # points enter none of the scalars
 
 
-@pytest.mark.parametrize("name", sorted(ref.TRACE_CASES))
+@pytest.mark.parametrize("name", sorted(cases.TRACE_CASES))
 def test_trace_matches_the_yardstick(name):
     p, e, xyz = _engine(name)
-    res_ref = ref.solve(p, xyz=xyz, max_num_iterations=50)
-    n_cmp = ref.compared_iterations(res_ref)
+    res_ref = lm.CameraBlocks(p, xyz=xyz).solve(max_num_iterations=50)
+    n_cmp = lm.compared_iterations(res_ref)
     assert n_cmp >= 4, "the case must give 4 clear iterations on the yardstick alone"
     with e:
         pts_before = (e.get_state()[1].tobytes(), e.get_points_world().tobytes())
@@ -120,7 +121,7 @@ def test_fixed_cost_on_a_dense_window():
     p.xyz = p.xyz + np.random.default_rng(0).normal(0.0, 0.01, p.xyz.shape)
     assert p.fixed_slot == 0 and p.n_obs == 4 * p.n_points
     sq = oracle.linearize(p, blocks=False)["block_sqnorm"]
-    c = ref.block_costs(p, sq)
+    c = lm.block_costs(p, sq)
     fixed_ref = float(c[p.obs_slot == 0].sum())
     assert fixed_ref > 0.0
     with make_engine(p) as e:
@@ -187,7 +188,7 @@ def test_refusals(small_window):
         with pytest.raises(EngineError, match="call order"):
             e.set_points_constant()
     # an empty program: only the constant camera has residual blocks
-    q = ref.tracking_problem(p, "zero", slot=0)
+    q = cases.tracking_problem(p, "zero", slot=0)
     with make_engine(q) as e:
         e.set_points_constant()
         with pytest.raises(EngineError, match="invalid argument.*No free camera has a residual block"):
@@ -216,38 +217,38 @@ def _feed(probe, imgs, depths, local, k):
     poses = None
     for i in range(k):
         got = probe.add(imgs[i], depths[i], local[i])
-        if len(got):
-            poses = got
+        if got is not None:
+            poses = got["poses"]
     return poses
 
 
 @pytest.mark.parametrize("levels", [1, 2])
 def test_track_frame_meets_the_bar_and_leaves_the_instance_alone(tmp_path, levels):
-    import track_probe
+    import host_class_probe
     k = 6
-    imgs, depths, T_gt, local = track_probe.sequence(k + 1, SEQ_SIZE, SEQ_K)
-    probe = track_probe.TrackProbe(tmp_path)
+    imgs, depths, T_gt, local = host_class_probe.sequence(k + 1, SEQ_SIZE, SEQ_K)
+    probe = host_class_probe.HostClassProbe(tmp_path)
     # a run that never calls trackFrame
     probe.create(levels, SEQ_SIZE, SEQ_K, window=4, radius=1, min_score=0.65)
     _feed(probe, imgs, depths, local, k)
-    plain = probe.add(imgs[k], depths[k], local[k])
+    plain = probe.add(imgs[k], depths[k], local[k])["poses"]
     assert len(plain) == k + 1
     # the same run with trackFrame in between
     probe.create(levels, SEQ_SIZE, SEQ_K, window=4, radius=1, min_score=0.65)
     _feed(probe, imgs, depths, local, k)
     for start, T0 in (("velocity", local[k - 1]), ("zero", np.eye(4))):
-        rot0, tr0 = track_probe.local_pose_error(T0, local[k])
+        rot0, tr0 = host_class_probe.local_pose_error(T0, local[k])
         T, info = probe.track(imgs[k], T0)
-        rot, tr = track_probe.local_pose_error(T, local[k])
+        rot, tr = host_class_probe.local_pose_error(T, local[k])
         print("levels %d from %s: start %.2e rad %.3f m -> end %.2e rad %.4f m; %s" % (levels, start, rot0, tr0, rot, tr, info))
         assert info["tracked"] and info["num_points"] >= 64
         assert info["final_cost"] <= info["initial_cost"]
-        assert tr <= ref.TRACK_BAR_M and rot <= ref.TRACK_BAR_RAD, (rot, tr)
+        assert tr <= cases.TRACK_BAR_M and rot <= cases.TRACK_BAR_RAD, (rot, tr)
     # more points asked for than there are: T_init comes back, tracked = false
     T, info = probe.track(imgs[k], local[k - 1], min_points=10 ** 7)
     assert not info["tracked"] and np.array_equal(T, local[k - 1]) and "too few" in info["message"]
     # const in effect: the following addFrame gives the byte-identical trajectory
-    after = probe.add(imgs[k], depths[k], local[k])
+    after = probe.add(imgs[k], depths[k], local[k])["poses"]
     assert after.tobytes() == plain.tobytes()
     probe.release()
 
@@ -257,16 +258,16 @@ def test_run_kitti_tracks_its_own_initial_poses(tmp_path):
     import os
     import re
     import subprocess
-    import track_probe
-    run = os.path.join(track_probe.PKG, "bin", "run_kitti")
+    import host_class_probe
+    run = os.path.join(host_class_probe.PKG, "bin", "run_kitti")
     n_frames = 12
-    imgs, depths, T_gt, local = track_probe.sequence(n_frames, SEQ_SIZE, SEQ_K)
+    imgs, depths, T_gt, local = host_class_probe.sequence(n_frames, SEQ_SIZE, SEQ_K)
     common = "maxNumPoints = 4096\nslidingWindowSize = 4\npatchRadius = 1\nminScore = 0.65\nrobustThreshold = 0.05\nverbose = 0\n"
 
     def go(name, n_lines, extra):
         d = os.path.join(str(tmp_path), name)
         os.makedirs(d)
-        track_probe.write_sequence(d, imgs, depths, SEQ_K, local, n_lines)
+        host_class_probe.write_sequence(d, imgs, depths, SEQ_K, local, n_lines)
         cfg = os.path.join(d, "test.cfg")
         with open(cfg, "w") as f:
             f.write("DataDirectory = %s\nTrajectory = %s/init.txt\n%s%s" % (d, d, common, extra))
@@ -285,10 +286,10 @@ def test_run_kitti_tracks_its_own_initial_poses(tmp_path):
         f_i = int(t[0])
         T = np.eye(4)
         T[:3, :] = np.array(t[4].split(), np.float64).reshape(3, 4)
-        rot, tr = track_probe.local_pose_error(T, local[f_i])
+        rot, tr = host_class_probe.local_pose_error(T, local[f_i])
         print("frame %d: tracked %s, %s points, %s iterations, start pose %.2e rad %.4f m from the ground truth" % (f_i, t[1], t[2], t[3], rot, tr))
         assert t[1] == "1"
-        assert tr <= ref.TRACK_BAR_M and rot <= ref.TRACK_BAR_RAD, (f_i, rot, tr)
+        assert tr <= cases.TRACK_BAR_M and rot <= cases.TRACK_BAR_RAD, (f_i, rot, tr)
     # the key absent = InitialPose = trajectory, byte for byte (poses and every Result)
     _, out_a, res_a = go("absent", None, "")
     _, out_b, res_b = go("trajectory", None, "InitialPose = trajectory\n")

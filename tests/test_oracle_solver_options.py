@@ -1,5 +1,5 @@
 """The oracle's trust-region loop at NON-default solver options (include/pba.h pba_solver_options) against an independent dense
-numpy Levenberg-Marquardt written from Ceres' documented rules: Jacobi scaling on/off, the LM diagonal clamp, the trust-region
+numpy Levenberg-Marquardt written from Ceres' documented rules (tests/lm_yardstick.py on the explicit Jacobian): Jacobi scaling on/off, the LM diagonal clamp, the trust-region
 radius bounds, the step-quality threshold, the three tolerances set to end the solve partway through, and the invalid-step path
 (a singular linear solve) up to max_num_consecutive_invalid_steps.
 
@@ -13,6 +13,8 @@ from scipy.spatial.transform import Rotation
 
 from oracle import oracle
 from photobundle_amd import imgproc, synthetic
+
+import lm_yardstick as lm
 
 TOLERANCES_OFF = dict(function_tolerance=0.0, gradient_tolerance=0.0, parameter_tolerance=0.0)
 MAX_IT = "Maximum number of iterations"
@@ -145,126 +147,27 @@ def check_case_shape(cid, ref, kind, n_it):
         assert not its[-1]["step_is_successful"]
 
 
-# ---- the independent dense loop --------------------------------------------------------------------------------------------------
-def _dense_system(p, cams, xyz):
-    P = p.patch_len
-    free = [c for c in range(p.n_frames) if c != p.fixed_slot]
-    cols_c = {c: 6 * i for i, c in enumerate(free)}
-    n_cam = 6 * len(free)
-    J = np.zeros((p.n_obs * P, n_cam + 3 * p.n_points))
-    r = np.zeros(p.n_obs * P)
-    for o in range(p.n_obs):
-        rb, jc, jp = oracle.eval_block(p, o, cams=cams, xyz=xyz)
-        s = rb @ rb
-        k = np.sqrt(p.huber / np.sqrt(s)) if p.huber > 0 and s > p.huber ** 2 else 1.0
-        rows = slice(o * P, (o + 1) * P)
-        r[rows] = k * rb
-        if p.obs_slot[o] in cols_c:
-            J[rows, cols_c[p.obs_slot[o]]:cols_c[p.obs_slot[o]] + 6] = k * jc
-        q = n_cam + 3 * p.obs_point[o]
-        J[rows, q:q + 3] = k * jp
-    return J, r, n_cam
-
-
-def _cost(p, cams, xyz):
-    s = oracle.linearize(p, cams=cams, xyz=xyz, blocks=False)["block_sqnorm"]
-    a = p.huber
-    return 0.5 * float(np.sum(np.where((a > 0) & (s > a * a), 2 * a * np.sqrt(s) - a * a, s)))
-
-
-def dense_lm(p, o):
-    """Ceres' TrustRegionMinimizer + LevenbergMarquardtStrategy on the full dense normal equations (no Schur complement), with
-    the options `o`.  A linear solve that fails (Cholesky of a matrix that is not positive definite) or a model cost change <= 0
-    is an INVALID step: the radius is divided by the decrease factor as for a rejected step, and the solve fails once
-    max_num_consecutive_invalid_steps of them follow each other.  Returns (log entries, termination kind, cams, xyz)."""
-    free = [c for c in range(p.n_frames) if c != p.fixed_slot]
-    cams, xyz = p.cams.copy(), p.xyz.copy()
-    cost = _cost(p, cams, xyz)
-    J, r, n_cam = _dense_system(p, cams, xyz)
-    gmax = np.abs(J.T @ r).max()
-    scale = 1.0 / (1.0 + np.sqrt((J * J).sum(0))) if o.jacobi_scaling else np.ones(J.shape[1])
-    radius, dec, n_invalid = o.initial_trust_region_radius, 2.0, 0
-    log = [dict(iteration=0, valid=1, successful=1, cost=cost, radius=radius)]
-
-    def finalize():
-        e = log[-1]
-        if e["iteration"] >= o.max_num_iterations:
-            return MAX_IT
-        if e["successful"] and gmax <= o.gradient_tolerance:
-            return GRAD
-        if radius <= o.min_trust_region_radius:
-            return MIN_RADIUS
-        return None
-
-    kind = finalize()
-    while kind is None:
-        iteration = log[-1]["iteration"] + 1
-        Js = J * scale
-        D2 = np.clip((Js * Js).sum(0), o.min_lm_diagonal, o.max_lm_diagonal) / radius
-        H = Js.T @ Js + np.diag(D2)
-        try:
-            L = np.linalg.cholesky(H)
-        except np.linalg.LinAlgError:
-            L = None
-        model_cost_change = 0.0
-        if L is not None:
-            step = -np.linalg.solve(L.T, np.linalg.solve(L, Js.T @ r))
-            model = Js @ step
-            model_cost_change = -model @ (r + model / 2)
-        if L is None or not model_cost_change > 0:
-            n_invalid += 1
-            if n_invalid >= o.max_num_consecutive_invalid_steps:
-                log.append(dict(iteration=iteration, valid=0, successful=0, cost=cost, radius=radius))
-                kind = INVALID
-                break
-            radius /= dec
-            dec *= 2.0
-            log.append(dict(iteration=iteration, valid=0, successful=0, cost=cost, radius=radius))
-            kind = finalize()
-            continue
-        n_invalid = 0
-        delta = step * scale
-        cand_c, cand_x = cams.copy(), xyz.copy()
-        for i, c in enumerate(free):
-            cand_c[c] += delta[6 * i: 6 * i + 6]
-        cand_x += delta[n_cam:].reshape(-1, 3)
-        new_cost = _cost(p, cand_c, cand_x)
-        x_norm = np.sqrt(sum((cams[c] ** 2).sum() for c in free) + (xyz ** 2).sum())
-        if np.linalg.norm(delta) <= o.parameter_tolerance * (x_norm + o.parameter_tolerance):
-            kind = PARAM
-            break
-        if abs(cost - new_cost) <= o.function_tolerance * cost:
-            kind = FUNC
-            break
-        rho = (cost - new_cost) / model_cost_change
-        if rho > o.min_relative_decrease:
-            cams, xyz, cost = cand_c, cand_x, new_cost
-            radius = min(o.max_trust_region_radius, radius / max(1.0 / 3.0, 1.0 - (2.0 * rho - 1.0) ** 3))
-            dec = 2.0
-            J, r, n_cam = _dense_system(p, cams, xyz)
-            gmax = np.abs(J.T @ r).max()
-            log.append(dict(iteration=iteration, valid=1, successful=1, cost=cost, radius=radius))
-        else:
-            radius /= dec
-            dec *= 2.0
-            log.append(dict(iteration=iteration, valid=1, successful=0, cost=new_cost, radius=radius))
-        kind = finalize()
-    return log, kind, cams, xyz
+# ---- the independent dense loop: lm_yardstick's loop on the explicit Jacobian --------------------------------------------------------
+KINDS = (MAX_IT, GRAD, MIN_RADIUS, INVALID, PARAM, FUNC)
 
 
 def compare_with_dense_loop(p, o, ref):
-    log, kind, cams, xyz = dense_lm(p, o)
+    res = lm.ExplicitJacobian(p).solve(**lm.options_of(o))
+    log, cams, xyz = res["iterations"], res["cams"], res["xyz"]
+    kind = next(k for k in KINDS if res["message"].startswith(k))
     its = ref["iterations"]
     assert ref["message"].startswith(kind), (kind, ref["message"])
     assert len(its) == len(log), (len(its), len(log), ref["message"])
     for a, b in zip(its, log):
         assert a["iteration"] == b["iteration"]
-        assert (a["step_is_valid"], a["step_is_successful"]) == (b["valid"], b["successful"]), a["iteration"]
+        assert (a["step_is_valid"], a["step_is_successful"]) == (b["step_is_valid"], b["step_is_successful"]), a["iteration"]
         # a rejected entry logs the candidate's cost: an overshooting step, where the cost is first-order sensitive to the step (which
         # the Schur path and the dense solve agree on to ~1e-8, test_oracle_solver.py)
-        assert np.isclose(a["cost"], b["cost"], rtol=1e-9 if b["successful"] or not b["valid"] else 1e-8), (a["iteration"], a["cost"], b["cost"])
-        assert np.isclose(a["trust_region_radius"], b["radius"], rtol=1e-9), (a["iteration"], a["trust_region_radius"], b["radius"])
-    assert ref["num_successful_steps"] == sum(b["successful"] for b in log)
+        assert np.isclose(a["cost"], b["cost"], rtol=1e-9 if b["step_is_successful"] or not b["step_is_valid"] else 1e-8), \
+            (a["iteration"], a["cost"], b["cost"])
+        assert np.isclose(a["trust_region_radius"], b["trust_region_radius"], rtol=1e-9), \
+            (a["iteration"], a["trust_region_radius"], b["trust_region_radius"])
+    assert ref["num_successful_steps"] == sum(b["step_is_successful"] for b in log)
     assert ref["termination_type"] == {INVALID: 2, MAX_IT: 1}.get(kind, 0)
     assert np.abs(ref["cams"] - cams).max() <= 1e-7 and np.allclose(ref["xyz"], xyz, rtol=1e-7, atol=1e-7)
     return log

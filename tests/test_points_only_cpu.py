@@ -1,4 +1,4 @@
-"""Structure-only solves (pba_set_cameras_constant) without a device: the numpy yardstick tests/points_only_ref.py against two
+"""Structure-only solves (pba_set_cameras_constant) without a device: the numpy yardstick tests/lm_yardstick.py (PointBlocks) against two
 independent routes (dense point-only normal equations from per-block oracle products; scipy.optimize.least_squares over the same 3 n
 parameters), the qualification of the device trace cases on the yardstick alone, and the ABI / Python / host plumbing of the mode."""
 import ctypes as C
@@ -10,16 +10,17 @@ import pytest
 from oracle import oracle
 from photobundle_amd import synthetic
 
-import points_only_ref as ref
+import lm_yardstick as lm
+import points_only_cases as cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("huber", [0.0, 0.05])
 def test_first_step_equals_the_dense_point_only_normal_equations(huber):
-    p = ref.cameras_to_ground_truth(synthetic.make_window(n_frames=3, n_points=40, radius=1, size=(96, 128), K=(150.0, 150.0, 64.0, 48.0),
+    p = cases.cameras_to_ground_truth(synthetic.make_window(n_frames=3, n_points=40, radius=1, size=(96, 128), K=(150.0, 150.0, 64.0, 48.0),
                                                           huber=huber, seed_offset=1))
-    st = ref.first_step(p, radius=1e4)
+    st = lm.PointBlocks(p).first_step(radius=1e4)
     # a second route: per-block products of the corrected rows, summed into ONE dense 3 n x 3 n system and solved densely
     bp = oracle.block_products(p, cams=p.cams, xyz=p.xyz)
     n = 3 * p.n_points
@@ -45,12 +46,12 @@ def test_first_step_equals_the_dense_point_only_normal_equations(huber):
     assert np.abs(st["gradient"].ravel() - g).max() <= tol * np.abs(g).max()
     assert st["linear_solver_ok"]
     sq = oracle.linearize(p, cams=p.cams, blocks=False)["block_sqnorm"]
-    assert np.isclose(st["cost"], ref.block_costs(p, sq).sum(), rtol=1e-14)
+    assert np.isclose(st["cost"], lm.block_costs(p, sq).sum(), rtol=1e-14)
 
 
 def _scipy_problem(seed):
     from test_oracle_scipy_minimum import _Restatement
-    p = ref.cameras_to_ground_truth(synthetic.make_window(n_frames=3, n_points=30, radius=1, size=(96, 128), K=(160.0, 160.0, 64.0, 48.0),
+    p = cases.cameras_to_ground_truth(synthetic.make_window(n_frames=3, n_points=30, radius=1, size=(96, 128), K=(160.0, 160.0, 64.0, 48.0),
                                                           rot_deg=0.05, trans=0.01, depth_noise=0.005, seed_offset=seed))
     rs = _Restatement(p)
     n_cam = rs.n_cam
@@ -62,7 +63,7 @@ def _scipy_problem(seed):
     def jacobian(x):
         return rs.jacobian(np.concatenate([tc, x]))[:, n_cam:]
 
-    res = ref.solve(p, max_num_iterations=400, function_tolerance=1e-14, gradient_tolerance=1e-14, parameter_tolerance=1e-14)
+    res = lm.PointBlocks(p).solve(max_num_iterations=400, function_tolerance=1e-14, gradient_tolerance=1e-14, parameter_tolerance=1e-14)
     return p, rs, residuals, jacobian, res
 
 
@@ -113,21 +114,21 @@ def test_yardstick_end_point_is_stationary_for_scipy(seed):
 def trace_runs():
     """The yardstick on every trace case, on autodiff evaluations: (problem, extras, rays, rho, result, compared iterations)."""
     out = {}
-    for name in ref.TRACE_CASES:
-        p, extras, rays, rho = ref.trace_case(name)
-        res = ref.solve(p, rays, rho, max_num_iterations=ref.REF_ITERATIONS)
-        out[name] = (p, extras, rays, rho, res, ref.compared_iterations(res))
+    for name in cases.TRACE_CASES:
+        p, extras, rays, rho = cases.trace_case(name)
+        res = lm.PointBlocks(p, rays, rho).solve(max_num_iterations=cases.REF_ITERATIONS)
+        out[name] = (p, extras, rays, rho, res, lm.compared_iterations(res))
     return out
 
 
-@pytest.mark.parametrize("name", sorted(ref.TRACE_CASES))
+@pytest.mark.parametrize("name", sorted(cases.TRACE_CASES))
 def test_trace_cases_have_four_clear_iterations(trace_runs, name):
     """The condition of the device trace test (tests/test_gpu_points_only.py), on the yardstick alone."""
     res, n_cmp = trace_runs[name][4:]
     assert n_cmp >= 4, [(i["step_is_successful"], i["relative_decrease"]) for i in res["iterations"]]
 
 
-@pytest.mark.parametrize("name", sorted(ref.TRACE_CASES))
+@pytest.mark.parametrize("name", sorted(cases.TRACE_CASES))
 def test_trace_cases_qualify(trace_runs, name):
     """A case qualifies for the device comparison when the yardstick itself is insensitive to how the derivatives are evaluated: run
     on analytic evaluations it takes the same decisions and ends the compared iterations within 1e-6 (a tenth of the device bar) of the
@@ -135,7 +136,7 @@ def test_trace_cases_qualify(trace_runs, name):
     amplifies its inverse depth by depth^2).  The single-observation case is held to cost and decisions only: its rank-2 blocks leave
     one direction per point to the damping alone."""
     p, extras, rays, rho, res, n_cmp = trace_runs[name]
-    ana = ref.solve(p, rays, rho, autodiff=False, max_num_iterations=n_cmp - 1)
+    ana = lm.PointBlocks(p, rays, rho, autodiff=False).solve(max_num_iterations=n_cmp - 1)
     a, b = res["iterations"][:n_cmp], ana["iterations"]
     assert len(b) == n_cmp
     assert [i["step_is_successful"] for i in a] == [i["step_is_successful"] for i in b]
@@ -150,15 +151,15 @@ def test_trace_cases_qualify(trace_runs, name):
 
 
 def test_the_wide_case_holds_a_point_seen_once_and_one_seen_by_every_frame():
-    p, _, _, _ = ref.trace_case("20-frames-r1-causal")
+    p, _, _, _ = cases.trace_case("20-frames-r1-causal")
     count = np.bincount(p.obs_point, minlength=p.n_points)
     assert count.min() == 1 and count.max() == 20 and p.n_frames == 20
 
 
 def test_a_rejecting_start_exists_on_the_yardstick():
     """The device test of rejected steps starts from a radius the yardstick rejects at least once."""
-    p, _, rays, rho = ref.trace_case("3-frames-r1-huber")
-    res = ref.solve(p, rays, rho, max_num_iterations=6, initial_trust_region_radius=1e12)
+    p, _, rays, rho = cases.trace_case("3-frames-r1-huber")
+    res = lm.PointBlocks(p, rays, rho).solve(max_num_iterations=6, initial_trust_region_radius=1e12)
     assert any(i["step_is_valid"] and not i["step_is_successful"] for i in res["iterations"][1:])
 
 
@@ -188,21 +189,21 @@ def test_python_wrappers_exist():
 
 
 def test_host_header_compiles_with_the_option(tmp_path):
-    import points_probe
-    probe = points_probe.PointsProbe(tmp_path)
-    for name in ("probe_points_create", "probe_points_add", "probe_points_print_options", "probe_points_release"):
+    import host_class_probe
+    probe = host_class_probe.HostClassProbe(tmp_path)
+    for name in ("probe_create", "probe_add", "probe_print_options", "probe_release"):
         assert hasattr(probe.L, name)
-    assert "camerasConstant = 1\n" in probe.print_options(True)
-    assert "camerasConstant = 0\n" in probe.print_options(False)
+    assert "camerasConstant = 1\n" in probe.print_options(cameras_constant=True)
+    assert "camerasConstant = 0\n" in probe.print_options(cameras_constant=False)
 
 
 def test_run_kitti_accepts_the_key_up_to_the_device(tmp_path):
     import subprocess
-    import track_probe
+    import host_class_probe
     run = os.path.join(ROOT, "photobundle_amd", "bin", "run_kitti")
     assert os.path.exists(run), "build photobundle_amd/bin/run_kitti first (__graft_entry__.build())"
     img = np.zeros((32, 48), np.uint8)
-    track_probe.write_sequence(str(tmp_path), [img], [np.ones((32, 48), np.float32)], (50.0, 50.0, 24.0, 16.0), [np.eye(4)])
+    host_class_probe.write_sequence(str(tmp_path), [img], [np.ones((32, 48), np.float32)], (50.0, 50.0, 24.0, 16.0), [np.eye(4)])
 
     def go(extra):
         cfg = os.path.join(str(tmp_path), "test.cfg")

@@ -1,4 +1,4 @@
-"""Pose-only solves (pba_set_points_constant) without a device: the numpy yardstick tests/pose_only_ref.py against two independent
+"""Pose-only solves (pba_set_points_constant) without a device: the numpy yardstick tests/lm_yardstick.py (CameraBlocks) against two independent
 routes (dense camera-only normal equations from per-block oracle rows; scipy.optimize.least_squares over the same 6 k parameters),
 the tracking bar on the yardstick itself, and the ABI / Python plumbing of the mode."""
 import ctypes as C
@@ -10,7 +10,8 @@ import pytest
 from oracle import oracle
 from photobundle_amd import synthetic
 
-import pose_only_ref as ref
+import lm_yardstick as lm
+import pose_only_cases as cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -39,7 +40,7 @@ def _dense_camera_system(p, cols):
 def test_first_step_equals_the_dense_camera_only_normal_equations(huber, fixed_slot):
     p = synthetic.make_window(n_frames=3, n_points=40, radius=1, size=(96, 128), K=(150.0, 150.0, 64.0, 48.0), huber=huber, seed_offset=1)
     p.fixed_slot = fixed_slot
-    st = ref.first_step(p, radius=1e4)
+    st = lm.CameraBlocks(p).first_step(radius=1e4)
     cols = st["cols"]
     assert cols == [c for c in range(3) if c != fixed_slot]
     J, r = _dense_camera_system(p, cols)
@@ -61,7 +62,7 @@ def test_first_step_equals_the_dense_camera_only_normal_equations(huber, fixed_s
     assert np.allclose(st["gradient"].ravel(), J.T @ r, rtol=1e-8, atol=1e-8 * np.abs(J.T @ r).max())
     # fixed cost: the loss-corrected cost of the constant camera's residual blocks
     sq = oracle.linearize(p, blocks=False)["block_sqnorm"]
-    c = ref.block_costs(p, sq)
+    c = lm.block_costs(p, sq)
     assert np.isclose(st["fixed_cost"], c[p.obs_slot == fixed_slot].sum(), rtol=1e-14)
     assert np.isclose(st["cost"] + st["fixed_cost"], c.sum(), rtol=1e-13)
 
@@ -84,7 +85,7 @@ def test_end_point_matches_scipy_least_squares_over_the_cameras():
         return rs.jacobian(np.concatenate([tc, xyz]))[:, :n_cam]
 
     theta0 = rs.pack(p.cams, p.xyz)[:n_cam]
-    res = ref.solve(p, max_num_iterations=400, function_tolerance=1e-14, gradient_tolerance=1e-14, parameter_tolerance=1e-14)
+    res = lm.CameraBlocks(p).solve(max_num_iterations=400, function_tolerance=1e-14, gradient_tolerance=1e-14, parameter_tolerance=1e-14)
     sp = least_squares(residuals, theta0, jac=jacobian, method="trf", x_scale="jac", ftol=1e-15, xtol=1e-15, gtol=1e-15, max_nfev=2000)
     full_sp = sp.cost      # scipy's residual vector holds every block, the constant camera's included (like final_cost)
     assert res["final_cost"] < res["initial_cost"] and full_sp < res["initial_cost"]
@@ -97,30 +98,30 @@ def test_end_point_matches_scipy_least_squares_over_the_cameras():
 
 
 @pytest.mark.parametrize("start", ["velocity", "zero"])
-@pytest.mark.parametrize("shape", sorted(ref.TRACKING_SHAPES))
+@pytest.mark.parametrize("shape", sorted(cases.TRACKING_SHAPES))
 def test_tracking_bar_on_the_yardstick(shape, start):
     """The last frame of a 5-frame window tracked against the window's points, from the constant-velocity prediction and from zero
     motion: the yardstick ends within 0.02 m and 0.1 degree of the ground truth (one sigma of make_window's trans / rot_deg
     defaults; the bar the device is held to as well)."""
-    w = ref.tracking_window(shape)
-    p = ref.tracking_problem(w, start)
+    w = cases.tracking_window(shape)
+    p = cases.tracking_problem(w, start)
     slot = p.meta["tracked_slot"]
     gt = w.meta["cams_gt"][slot]
-    rot0, tr0 = ref.pose_error(p.cams[slot], gt)
-    res = ref.solve(p, max_num_iterations=50)
-    rot, tr = ref.pose_error(res["cams"][slot], gt)
+    rot0, tr0 = cases.pose_error(p.cams[slot], gt)
+    res = lm.CameraBlocks(p).solve(max_num_iterations=50)
+    rot, tr = cases.pose_error(res["cams"][slot], gt)
     print("%s from %s: start %.2e rad %.3f m -> end %.2e rad %.4f m in %d iterations (%s)" % (shape, start, rot0, tr0, rot, tr,
                                                                                            len(res["iterations"]) - 1, res["message"]))
-    assert ref.program_cameras(p) == [slot]
-    assert tr <= ref.TRACK_BAR_M and rot <= ref.TRACK_BAR_RAD, (rot, tr)
+    assert lm.CameraBlocks(p).cols == [slot]
+    assert tr <= cases.TRACK_BAR_M and rot <= cases.TRACK_BAR_RAD, (rot, tr)
     others = [c for c in range(p.n_frames) if c != slot]
     assert np.array_equal(res["cams"][others], p.cams[others])
 
 
 def test_empty_program_is_refused_by_the_yardstick(small_window):
-    p = ref.tracking_problem(small_window, "zero", slot=0)      # only the constant camera has residual blocks
+    p = cases.tracking_problem(small_window, "zero", slot=0)      # only the constant camera has residual blocks
     with pytest.raises(ValueError, match="empty program"):
-        ref.solve(p)
+        lm.CameraBlocks(p).solve()
 
 
 # ---- ABI and plumbing without a device ------------------------------------------------------------------------------------------------
@@ -143,20 +144,19 @@ def test_python_wrapper_exists():
     assert callable(getattr(Engine, "set_points_constant"))
 
 
-@pytest.mark.parametrize("name", sorted(ref.TRACE_CASES))
+@pytest.mark.parametrize("name", sorted(cases.TRACE_CASES))
 def test_trace_cases_have_four_clear_iterations(name):
     """The condition of the device trace test (tests/test_gpu_pose_only.py), on the yardstick alone: every case has at least 4 iterations
     before the first one whose decision hinges on the last bits."""
-    p, _ = ref.trace_case(name)
-    res = ref.solve(p, max_num_iterations=50)
-    assert ref.compared_iterations(res) >= 4, [(i["step_is_successful"], i["relative_decrease"]) for i in res["iterations"]]
+    p, _ = cases.trace_case(name)
+    res = lm.CameraBlocks(p).solve(max_num_iterations=50)
+    assert lm.compared_iterations(res) >= 4, [(i["step_is_successful"], i["relative_decrease"]) for i in res["iterations"]]
 
 
 def test_host_header_compiles_with_trackframe_called(tmp_path):
-    import track_probe
-    so = track_probe.build(tmp_path)
-    L = C.CDLL(so)
-    for name in ("probe_track_create", "probe_track_add", "probe_track_track", "probe_track_defaults"):
+    import host_class_probe
+    L = host_class_probe.HostClassProbe(tmp_path).L
+    for name in ("probe_create", "probe_add", "probe_track", "probe_track_defaults"):
         assert hasattr(L, name)
 
 
@@ -169,9 +169,9 @@ def _run_kitti(args):
 
 
 def _tiny_sequence(tmp, extra):
-    import track_probe
+    import host_class_probe
     img = np.zeros((32, 48), np.uint8)
-    track_probe.write_sequence(str(tmp), [img], [np.ones((32, 48), np.float32)], (50.0, 50.0, 24.0, 16.0), [np.eye(4)])
+    host_class_probe.write_sequence(str(tmp), [img], [np.ones((32, 48), np.float32)], (50.0, 50.0, 24.0, 16.0), [np.eye(4)])
     cfg = os.path.join(str(tmp), "test.cfg")
     with open(cfg, "w") as f:
         f.write("DataDirectory = %s\nTrajectory = %s/init.txt\nverbose = 0\n%s" % (tmp, tmp, extra))
