@@ -45,7 +45,7 @@ typedef enum pba_status {
   PBA_ERR_NO_DEVICE = -3,   /* no gfx950 device visible: there is NO CPU fallback */
   PBA_ERR_STATE = -4,       /* call order violated (e.g. solve before set_problem) */
   PBA_ERR_COMM = -5,        /* collective transport error */
-  PBA_ERR_NUMERIC = -6      /* non-finite evaluation at the initial point */
+  PBA_ERR_NUMERIC = -6      /* non-finite evaluation at the initial point; pba_covariance: singular normal matrix */
 } pba_status;
 
 /* Replaces the constructor arguments of PhotometricBundleAdjustment (photobundle.h:148) that matter on the
@@ -328,6 +328,47 @@ int pba_get_obs_records(pba_engine* e, double* rec6);
 /* ---- the LM loop: replaces ceres::Solve (photobundle.cc:829) --------------------------------------------- */
 int pba_solve(pba_engine* e, const pba_solver_options* o, pba_solver_summary* summary,
               pba_iteration_summary* iterations, int32_t max_iterations_out);
+
+/* ---- covariance output: replaces ceres::Covariance::Compute + GetCovarianceBlock after ceres::Solve ------------
+ * Blocks of (J^T J)^-1 of the reduced program of the mode that is on, J the loss-corrected Jacobian (sqrt(rho') row scaling) at the
+ * current (best) state, the one pba_get_state returns.  No damping, no Jacobi scaling, unit residual variance: the caller scales by
+ * its own sigma^2 (num_residuals, num_parameters and cost are there for 2 cost / (m - n)).  Camera blocks are in the engine's camera
+ * parameters: angle-axis and translation of the WORLD->CAMERA transform.
+ *   cam_cov    dense n_cam x n_cam, row-major, symmetric bit for bit.  Columns: the program's camera columns in ascending slot order --
+ *              full mode: the slots outside the anchor mask (the layout of pba_get_reduced_system); pose-only mode: the free cameras
+ *              that have a residual block.
+ *   point_cov  [n_points][9] row-major 3x3; in the inverse-depth mode entry 0 is set and the rest are zero (the convention of
+ *              pba_get_point_system).  Camera x point cross blocks are not computed.
+ * Full mode (any anchor mask, 2..32 slots), H = [U W; W^T V]: Sigma_cc = S^-1 with S = U - sum_p W_p V_p^-1 W_p^T;
+ * Sigma_pp(i) = V_i^-1 + (V_i^-1 W_i^T) Sigma_cc (W_i V_i^-1), W_i over the free cameras that observe point i (a point seen by
+ * anchored cameras only: V_i^-1).  Pose-only mode: blockdiag(U_a^-1), point_cov must be NULL.  Structure-only mode: V_i^-1 (1x1 with
+ * inverse depths), cam_cov must be NULL.  Either output pointer and info may be NULL.
+ * Every block (S, every V_i) is factorised in its UNIT-DIAGONAL form D^-1/2 A D^-1/2, D = diag A, and the inverse is unscaled again,
+ * so the reported pivots are scale-free numbers in (0, 1]; a pivot is the diagonal entry the Cholesky takes the root of.  The library
+ * applies no threshold of its own: a gauge-open window (one constant frame) can pass by rounding with a pivot near 1e-12 and a
+ * meaningless inverse -- min_cam_pivot and min_point_pivot are the caller's to judge.  Every sum has a fixed order: two fresh engines
+ * give the same bits.
+ * The call runs pba_linearize (the engine then holds a valid linearisation at the current point) and moves nothing else of the LM
+ * state: scales, radius bookkeeping, candidate parity, pba_solve_driver.  It writes device buffers of its own.  The one counter that
+ * can move is the one pba_linearize moves: when the current point had no valid linearisation, the Jacobian pass the call has to run
+ * counts as a linearisation (pba_counters.linearize_launches under profiling, and the pass count the NEXT pba_solve resets before it
+ * reports summary.num_jacobian_passes); after a pba_solve or a pba_linearize the point has one and nothing is counted.
+ * PBA_ERR_INVALID with a message in pba_last_error, before any launch: a non-NULL pointer for a block family the mode holds constant;
+ * a free camera of the full mode without a residual block (its block of H is zero; the message names the slot); multi-rank engines;
+ * the precision-sweep flags; the inverse-depth parameterisation in the full mode.  PBA_ERR_STATE as pba_linearize gives it.
+ * PBA_ERR_NUMERIC: a non-positive or non-finite pivot in any block -- H is singular, nothing is written to cam_cov / point_cov, and
+ * info names the first offender (point blocks are examined before the camera matrix). */
+typedef struct pba_covariance_info {
+  int32_t n_cam;            /* rows of cam_cov: 6 x the program's camera columns; 0 in the structure-only mode */
+  int32_t point_dim;        /* 3; 1 in the inverse-depth mode; 0 in the pose-only mode */
+  int32_t num_residuals, num_parameters;   /* of the program, so that a caller can form 2 cost / (m - n) */
+  double  cost;             /* program cost at the point (no fixed_cost) */
+  double  min_cam_pivot;    /* smallest Cholesky pivot of the UNIT-DIAGONAL camera matrix, in (0, 1]; 1 when n_cam = 0 */
+  double  min_point_pivot;  /* the same over all point blocks; 1 when the points are constant */
+  int32_t failed_is_point, failed_index;   /* after PBA_ERR_NUMERIC: where the first non-positive / non-finite pivot was (point
+                                            * index, or row of cam_cov); else 0, -1 */
+} pba_covariance_info;
+int pba_covariance(pba_engine* e, double* cam_cov, double* point_cov, pba_covariance_info* info);
 
 /* ---- several independent windows on one device ------------------------------------------------------------ */
 #define PBA_MAX_BATCH 64

@@ -14,6 +14,7 @@
 #include "pba_batch.h"
 #include "pba_pose.h"
 #include "pba_points.h"
+#include "pba_cov.h"
 
 #include <algorithm>
 #include <chrono>
@@ -172,6 +173,18 @@ struct pba_engine : pba::Handle {      // (device, stream, err, mem, events)
   double* d_pts_part = nullptr;     // [waves of k_points_solve][kPointsRow]
   double* d_pts_V = nullptr;        // [n_points][9] test hook (pba_config.flags bit 0)
   double* d_pts_rhs = nullptr;      // [n_points][3]
+
+  // covariance output (pba_covariance, pba_cov.h): everything on first use, nothing shared with the LM
+  double* d_cov_P = nullptr;        // [n_points][6] V^-1
+  double* d_cov_X = nullptr;        // [n_points][6] its triangular factor
+  double* d_cov_part = nullptr;     // [point blocks][kCovPart]
+  double* d_cov_S = nullptr;        // [n][n] undamped, unscaled reduced camera matrix
+  double* d_cov_C = nullptr;        // [n][n] its inverse
+  double* d_cov_pp = nullptr;       // [n_points][9]
+  double* d_cov_info = nullptr;     // [2] (k_cov_invert)
+  static constexpr int kCovKernels = 4;    // k_cov_point, k_cov_schur, k_cov_invert, k_cov_points
+  hipEvent_t cov_ev[2 * kCovKernels] = {}; // event profiling (pba_set_profiling(e, 1)): begin / end of each, created on first use
+  double cov_ms[kCovKernels] = {0, 0, 0, 0};   // ... of the last pba_covariance, -1: the kernel did not run
 
   // batched solves (pba_solve_batch, pba_batch.h): the window table lives with the batch's FIRST engine (grow-only), whose stream
   // carries the batch; while a batch runs every engine's `stream` names that stream and `stream_own` keeps its own
@@ -1856,6 +1869,164 @@ int pba_get_reduced_system(pba_engine* e, double* S, double* rhs, int32_t* n_out
   if (rhs) HIP_TRY(e, hipMemcpyAsync(rhs, e->d_rhs, sizeof(double) * n, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   return PBA_OK;
+}
+
+// Covariance output (pba_cov.h).  Every refusal comes before the first launch; the Jacobian pass is pba_linearize's; the kernels write
+// covariance-owned buffers only, and the host copies the results out once every pivot is known to be positive.
+int pba_covariance(pba_engine* e, double* cam_cov, double* point_cov, pba_covariance_info* info) {
+  if (!e) return PBA_ERR_INVALID;
+  pba_covariance_info inf{};
+  inf.min_cam_pivot = 1.0; inf.min_point_pivot = 1.0; inf.failed_index = -1;
+  if (info) *info = inf;
+  const bool pose = e->points_const, structure = e->cams_const;
+  if (e->comm.multi()) return fail(e, PBA_ERR_INVALID, "pba_covariance: multi-rank engines (pba_comm_*) are not built for the covariance output");
+  if ((e->cfg.flags >> 1) & 3)
+    return fail(e, PBA_ERR_INVALID, "pba_covariance: the precision-sweep sampler modes (pba_config.flags bits 1-2) are not built for the covariance output");
+  if (pose && point_cov)
+    return fail(e, PBA_ERR_INVALID, "pba_covariance: the points are constant (pba_set_points_constant): point_cov must be NULL");
+  if (structure && cam_cov)
+    return fail(e, PBA_ERR_INVALID, "pba_covariance: the cameras are constant (pba_set_cameras_constant): cam_cov must be NULL");
+  if (!pose && !structure && e->inverse_depth)
+    return fail(e, PBA_ERR_INVALID, "pba_covariance: the inverse-depth mode (pba_set_inverse_depth) with free cameras is not built; the "
+                                    "cameras-constant mode takes it");
+  { const int rc0 = check_ready(e, "pba_covariance"); if (rc0) return rc0; }
+  // the program's camera columns in ascending slot order
+  CovSchurParams cs{};
+  CovPointsParams cp{};
+  int n_cols = 0;
+  uint32_t cost_mask = 0xffffffffu;
+  for (int s = 0; s < kMaxFramesWide; ++s) cp.col_of_slot[s] = -1;
+  if (!structure) {
+    if (pose) cost_mask = 0;
+    for (int s = 0; s < e->n_frames; ++s) {
+      if (!slot_is_free(e->anchor_mask, s)) continue;
+      if (pose) cost_mask |= 1u << s;
+      if (!((e->slot_mask >> s) & 1u)) {
+        if (pose) continue;      // (Ceres: a parameter block without a residual block is not in the program)
+        return fail(e, PBA_ERR_INVALID, "pba_covariance: free camera slot %d has no residual block: its block of the normal matrix is zero; "
+                                        "hold it constant (pba_set_cameras_anchored)", s);
+      }
+      cp.col_of_slot[s] = (int8_t)n_cols;
+      cs.slot_of_col[n_cols++] = (uint8_t)s;
+    }
+    if (n_cols == 0) return fail(e, PBA_ERR_INVALID, "pba_covariance: no free camera has a residual block");
+  }
+  const int n = 6 * n_cols;
+  const int dim = e->inverse_depth ? 1 : 3;
+  const int pt_blocks = (e->n_points + kCovThreads - 1) / kCovThreads;
+  PBA_ENTER(e);
+  if (n > 0) {
+    int lds_max = 0;
+    const size_t need = cov_invert_smem_bytes(n) + 64;
+    if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, e->cfg.device) == hipSuccess && lds_max > 0 && need > (size_t)lds_max)
+      return fail(e, PBA_ERR_INVALID, "pba_covariance: %d camera columns need %zu bytes of LDS for the inverse, the device offers %d per workgroup", n_cols, need, lds_max);
+  }
+  int rc;
+  if ((rc = pba_linearize(e, nullptr))) return rc;
+  const int cur = e->cur;
+  if ((rc = dev_alloc(e, &e->d_cov_part, (size_t)kCovPart * pt_blocks))) return rc;
+  if (!pose) {
+    if ((rc = dev_alloc(e, &e->d_cov_P, (size_t)6 * e->n_points))) return rc;
+    if ((rc = dev_alloc(e, &e->d_cov_X, (size_t)6 * e->n_points))) return rc;
+    if ((rc = dev_alloc(e, &e->d_cov_pp, (size_t)9 * e->n_points))) return rc;
+  }
+  if (n > 0) {
+    if ((rc = dev_alloc(e, &e->d_cov_S, (size_t)n * n))) return rc;
+    if ((rc = dev_alloc(e, &e->d_cov_C, (size_t)n * n))) return rc;
+    if ((rc = dev_alloc(e, &e->d_cov_info, (size_t)2))) return rc;
+  }
+  const double* rays = e->inverse_depth ? e->d_rays : nullptr;
+  CovPointParams pp{};
+  pp.xyz = e->d_xyz[cur]; pp.rays = rays; pp.geom = e->d_geom[cur]; pp.rec = e->d_rec[cur]; pp.pt_begin = e->d_pt_begin; pp.obs_slot = e->d_obs_slot;
+  pp.P = pose ? nullptr : e->d_cov_P; pp.X = pose ? nullptr : e->d_cov_X; pp.pp = structure ? e->d_cov_pp : nullptr; pp.part = e->d_cov_part; pp.rec_stride = e->rec_stride;
+  pp.n_points = e->n_points; pp.n_frames = e->n_frames; pp.dim = dim; pp.cost_mask = cost_mask; pp.fx = e->cfg.fx; pp.fy = e->cfg.fy;
+  // event profiling: one begin / end pair per kernel, read back at the end of the call (pba_internal_covariance_times)
+  const bool timed = e->profile;
+  bool ran[pba_engine::kCovKernels] = {false, false, false, false};
+  if (timed && !e->cov_ev[0])
+    for (int k = 0; k < 2 * pba_engine::kCovKernels; ++k) { if ((rc = handle_event(e, &e->cov_ev[k]))) return rc; }
+  auto mark = [&](int k, int end) { if (timed) { (void)hipEventRecord(e->cov_ev[2 * k + end], e->stream); ran[k] = true; } };
+  auto collect = [&]() {
+    for (int k = 0; k < pba_engine::kCovKernels; ++k) {
+      float ms = 0.0f;
+      e->cov_ms[k] = (timed && ran[k] && hipEventElapsedTime(&ms, e->cov_ev[2 * k], e->cov_ev[2 * k + 1]) == hipSuccess) ? (double)ms : -1.0;
+    }
+  };
+  mark(0, 0);
+  hipLaunchKernelGGL(k_cov_point, dim3(pt_blocks), dim3(kCovThreads), 0, e->stream, pp);
+  mark(0, 1);
+  if (n > 0) {
+    cs.xyz = e->d_xyz[cur]; cs.rays = rays; cs.geom = e->d_geom[cur]; cs.rec = e->d_rec[cur]; cs.pt_begin = e->d_pt_begin; cs.obs_slot = e->d_obs_slot;
+    cs.X = pose ? nullptr : e->d_cov_X; cs.S = e->d_cov_S; cs.rec_stride = e->rec_stride;
+    cs.n_points = e->n_points; cs.n_frames = e->n_frames; cs.n_cols = n_cols; cs.fx = e->cfg.fx; cs.fy = e->cfg.fy;
+    // pose-only mode: S = blockdiag(U_a), the zero blocks by a memset and one workgroup per diagonal block
+    cs.diag_only = pose ? 1 : 0;
+    mark(1, 0);
+    if (pose) HIP_TRY(e, hipMemsetAsync(e->d_cov_S, 0, sizeof(double) * n * n, e->stream));
+    hipLaunchKernelGGL(k_cov_schur, dim3(pose ? n_cols : n_cols * (n_cols + 1) / 2), dim3(kCovThreads), 0, e->stream, cs);
+    mark(1, 1);
+    CovInvertParams ci{};
+    ci.S = e->d_cov_S; ci.C = e->d_cov_C; ci.info = e->d_cov_info; ci.n = n;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cov_invert), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cov_invert_smem_bytes(n));
+    (void)hipGetLastError();
+    mark(2, 0);
+    hipLaunchKernelGGL(k_cov_invert, dim3(1), dim3(kCovInvertT), cov_invert_smem_bytes(n), e->stream, ci);
+    mark(2, 1);
+  }
+  // the first pass decides: nothing is launched on the inverse of a singular matrix, nothing is copied out
+  std::vector<double> part((size_t)kCovPart * pt_blocks);
+  double cinfo[2] = {1.0, -1.0};
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipMemcpyAsync(part.data(), e->d_cov_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, e->stream));
+  if (n > 0) HIP_TRY(e, hipMemcpyAsync(cinfo, e->d_cov_info, sizeof(cinfo), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  double cost = 0.0, bad_pt = kCovNone;
+  for (int k = 0; k < pt_blocks; ++k) {      // block order
+    inf.min_point_pivot = std::min(inf.min_point_pivot, part[(size_t)kCovPart * k]);
+    bad_pt = std::min(bad_pt, part[(size_t)kCovPart * k + 1]);
+    cost += part[(size_t)kCovPart * k + 2];
+  }
+  inf.n_cam = n;
+  inf.point_dim = pose ? 0 : dim;
+  inf.num_residuals = (int32_t)(pba_internal_program_blocks(e) * pba_internal_patch_len(e));
+  inf.num_parameters = n + (pose ? 0 : dim * e->n_points);
+  inf.cost = cost;
+  inf.min_cam_pivot = n > 0 ? cinfo[0] : 1.0;
+  if (bad_pt < kCovNone) {
+    collect();
+    inf.failed_is_point = 1; inf.failed_index = (int32_t)bad_pt; inf.min_point_pivot = 0.0;
+    if (info) *info = inf;
+    return fail(e, PBA_ERR_NUMERIC, "pba_covariance: the block of point %d is not positive definite (non-positive or non-finite pivot): "
+                                    "the normal matrix is singular", inf.failed_index);
+  }
+  if (n > 0 && cinfo[1] >= 0.0) {
+    collect();
+    inf.failed_is_point = 0; inf.failed_index = (int32_t)cinfo[1];
+    if (info) *info = inf;
+    return fail(e, PBA_ERR_NUMERIC, "pba_covariance: non-positive or non-finite pivot at camera column %d (slot %d, parameter %d): the "
+                                    "normal matrix is singular; is the gauge fixed?", inf.failed_index, (int)cs.slot_of_col[inf.failed_index / 6], inf.failed_index % 6);
+  }
+  if (point_cov && !pose && !structure) {
+    cp.xyz = e->d_xyz[cur]; cp.geom = e->d_geom[cur]; cp.rec = e->d_rec[cur]; cp.pt_begin = e->d_pt_begin; cp.obs_slot = e->d_obs_slot;
+    cp.P = e->d_cov_P; cp.C = e->d_cov_C; cp.pp = e->d_cov_pp; cp.rec_stride = e->rec_stride;
+    cp.n_points = e->n_points; cp.n_frames = e->n_frames; cp.n = n; cp.fx = e->cfg.fx; cp.fy = e->cfg.fy;
+    mark(3, 0);
+    hipLaunchKernelGGL(k_cov_points, dim3(pt_blocks), dim3(kCovThreads), 0, e->stream, cp);
+    mark(3, 1);
+    HIP_TRY(e, hipGetLastError());
+  }
+  if (cam_cov) HIP_TRY(e, hipMemcpyAsync(cam_cov, e->d_cov_C, sizeof(double) * n * n, hipMemcpyDeviceToHost, e->stream));
+  if (point_cov) HIP_TRY(e, hipMemcpyAsync(point_cov, e->d_cov_pp, sizeof(double) * 9 * e->n_points, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  collect();
+  if (info) *info = inf;
+  return PBA_OK;
+}
+
+// Event time [ms] of the four kernels of the LAST pba_covariance (k_cov_point, k_cov_schur with its memset in the pose-only mode,
+// k_cov_invert, k_cov_points), -1 for a kernel that did not run or when event profiling (pba_set_profiling(e, 1)) was off.
+void pba_internal_covariance_times(const pba_engine* e, double* ms4) {
+  for (int k = 0; k < pba_engine::kCovKernels; ++k) ms4[k] = e->cov_ms[k];
 }
 
 int pba_get_obs_records(pba_engine* e, double* rec6) {

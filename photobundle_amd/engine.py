@@ -299,6 +299,28 @@ class Engine:
                              for i in range(s.num_iterations)]
         return res
 
+    # ---- covariance output -----------------------------------------------------------------------------------
+    def covariance(self, cameras=True, points=True):
+        """pba_covariance: blocks of (J^T J)^-1 of the reduced program at the current state (include/pba.h).  Returns a dict with
+        cam_cov [n, n] (None when not asked for), point_cov [n_points, 3, 3] (None likewise) and the fields of pba_covariance_info.
+        Raises EngineError with the status and message otherwise; its `status` and `info` attributes carry the status code and
+        the info fields (after PBA_ERR_NUMERIC: the first offender and the pivots)."""
+        info = _lib.CovarianceInfo()
+        n_max = 6 * 32
+        cam = np.zeros(n_max * n_max) if cameras else None
+        pts = np.zeros((self.n_points, 3, 3)) if points else None
+        rc = self._L.pba_covariance(self._h, _ptr(cam) if cameras else None, _ptr(pts) if points else None, C.byref(info))
+        fields = {f: getattr(info, f) for f, _ in _lib.CovarianceInfo._fields_}
+        if rc != 0:
+            err = EngineError("pba_covariance: %s (%s)" % (self._L.pba_status_string(rc).decode(), self._L.pba_last_error(self._h).decode()))
+            err.status, err.info = rc, fields
+            raise err
+        n = info.n_cam
+        out = dict(fields)
+        out["cam_cov"] = cam[:n * n].reshape(n, n).copy() if cameras else None
+        out["point_cov"] = pts
+        return out
+
     # ---- multi-GPU -------------------------------------------------------------------------------------------
     @staticmethod
     def comm_unique_id():

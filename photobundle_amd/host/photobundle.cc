@@ -17,6 +17,7 @@
 #include <omp.h>
 #include <map>
 #include <stdexcept>
+#include <unordered_map>
 
 #include "../../include/pba.h"
 #include "imgproc.h"
@@ -170,7 +171,8 @@ PhotometricBundleAdjustment::Options::Options(const utils::ConfigFile& cf)
       verbose((bool)cf.get<int>("verbose", 1)),
       device(cf.get<int>("device", 0)),
       camerasConstant((bool)cf.get<int>("camerasConstant", 0)),
-      numConstantFrames(cf.get<int>("numConstantFrames", 1)) {}
+      numConstantFrames(cf.get<int>("numConstantFrames", 1)),
+      computeCovariance((bool)cf.get<int>("computeCovariance", 0)) {}
 
 std::ostream& operator<<(std::ostream& os, const PhotometricBundleAdjustment::Options& o) {
   using DT = PhotometricBundleAdjustment::Options::DescriptorType;
@@ -180,7 +182,8 @@ std::ostream& operator<<(std::ostream& os, const PhotometricBundleAdjustment::Op
      << "\nmaxValidDepth = " << o.maxValidDepth << "\nslidingWindowSize = " << o.slidingWindowSize << "\npatchRadius = " << o.patchRadius
      << "\ndoGaussianWeighting = " << (o.doGaussianWeighting ? 1 : 0) << "\nrobustThreshold = " << o.robustThreshold
      << "\ndescriptorType = " << dt << "\nnumThreads = " << o.numThreads << "\nverbose = " << (o.verbose ? 1 : 0) << "\ndevice = " << o.device
-     << "\ncamerasConstant = " << (o.camerasConstant ? 1 : 0) << "\nnumConstantFrames = " << o.numConstantFrames << "\n";
+     << "\ncamerasConstant = " << (o.camerasConstant ? 1 : 0) << "\nnumConstantFrames = " << o.numConstantFrames
+     << "\ncomputeCovariance = " << (o.computeCovariance ? 1 : 0) << "\n";
   return os;
 }
 
@@ -266,6 +269,9 @@ PhotometricBundleAdjustment::PhotometricBundleAdjustment(const Calibration& cali
   if (options.numConstantFrames < 1 || options.numConstantFrames > options.slidingWindowSize - 1)
     throw std::invalid_argument("numConstantFrames = " + std::to_string(options.numConstantFrames) + " is outside 1 .. slidingWindowSize - 1 = " +
                                 std::to_string(options.slidingWindowSize - 1) + ": at least one frame of the window must stay free");
+  if (options.computeCovariance && options.numConstantFrames < 2 && !options.camerasConstant)
+    throw std::invalid_argument("computeCovariance needs numConstantFrames >= 2 or camerasConstant: with one constant frame the gauge is open (the "
+                                "scale of the window is free) and the normal matrix is singular");
   // Multi-channel descriptor types: the reference's debug builds stop at `assert(p0.size() == w.size())`
   // (photobundle.cc:684: C P descriptor entries against P patch weights); its release builds run, with the weights
   // restarting per channel (:714-721), and that is what is built here.
@@ -351,6 +357,18 @@ Mat44 PhotometricBundleAdjustment::trackFrame(const uint8_t* image, const Mat44&
   tr.message = summary.message;
   tr.tracked = summary.termination_type != 2;      // (2: FAILURE)
   if (!tr.tracked) return T_init;
+  if (topt.computeCovariance) {
+    pba_covariance_info info;
+    double cov[36];
+    const int rcc = pba_covariance(e, cov, nullptr, &info);
+    if (rcc == PBA_OK && info.n_cam == 6) {
+      std::memcpy(tr.covariance, cov, sizeof(cov));
+      tr.minPivot = info.min_cam_pivot;
+      tr.covarianceOk = true;
+    } else {
+      tr.covarianceMessage = rcc == PBA_OK ? std::string("unexpected number of camera columns") : std::string(pba_status_string(rcc)) + " (" + pba_last_error(e) + ")";
+    }
+  }
   // back to addFrame's convention: T_i = inv(T_w_i) * T_w_(i-1) with inv(T_w_i) = the refined camera block
   return ParamsToPose(cams + 6) * T_prev;
 }
@@ -630,6 +648,11 @@ struct PhotometricBundleAdjustment::OptimizeState {
   pba_solver_options so;
   pba_solver_summary summary;
   std::vector<pba_iteration_summary> its;
+  // Options::computeCovariance: pba_covariance at the refined state (optimizeFinish)
+  bool cov_ok = false;
+  std::string cov_message;
+  pba_covariance_info cov_info;
+  std::vector<double> cam_cov, point_cov;
   void lap(int k) { const double t = wall_ms(); t_o[k] += t - t_lo; t_lo = t; }
 };
 
@@ -766,6 +789,13 @@ void PhotometricBundleAdjustment::optimizeFinish(OptimizeState& st, Result* resu
     const bool cams_const = _options_ptr->camerasConstant;
     check(_engine, pba_get_state(_engine, cams_const ? nullptr : cams.data(), xyz.data()), "pba_get_state");
     for (size_t i = 0; i < selected.size(); ++i) for (int k = 0; k < 3; ++k) selected[i]->X[k] = xyz[3 * i + k];
+    if (_options_ptr->computeCovariance) {
+      st.point_cov.assign(9 * selected.size(), 0.0);
+      if (!cams_const) st.cam_cov.assign((size_t)36 * window * window, 0.0);
+      const int rc = pba_covariance(_engine, cams_const ? nullptr : st.cam_cov.data(), st.point_cov.data(), &st.cov_info);
+      st.cov_ok = rc == PBA_OK;
+      if (!st.cov_ok) st.cov_message = std::string(pba_status_string(rc)) + " (" + pba_last_error(_engine) + ")";
+    }
     // put back the refined camera poses (:841-844)
     if (!cams_const) {
       // (anchor frames did not move: their poses stay as they are -- no parameter round trip)
@@ -807,6 +837,47 @@ void PhotometricBundleAdjustment::optimizeFinish(OptimizeState& st, Result* resu
       o.iteration_time_in_seconds = s.iteration_time_in_seconds; o.step_solver_time_in_seconds = s.step_solver_time_in_seconds;
       o.cumulative_time_in_seconds = s.cumulative_time_in_seconds;
       result->iterationSummary.push_back(o);
+    }
+    result->covarianceOk = st.cov_ok;
+    result->covarianceMessage = st.cov_message;
+    result->minCameraPivot = st.cov_ok ? st.cov_info.min_cam_pivot : 0.0;
+    result->minPointPivot = st.cov_ok ? st.cov_info.min_point_pivot : 0.0;
+    result->covarianceFrameIds.clear();
+    result->poseCovariance.clear();
+    result->refinedPointCovariances.clear();
+    if (st.cov_ok) {
+      // camera columns come in ascending ring slot; the result lists the free frames in ascending frame id
+      if (!_options_ptr->camerasConstant) {
+        const uint32_t n_const = (uint32_t)std::max(1, st.n_anchored);
+        std::vector<int> col_of_slot((size_t)window, -1);
+        std::vector<uint32_t> free_slots;
+        for (uint32_t id = frame_id_start + n_const; id <= frame_id_end; ++id) free_slots.push_back(id % (uint32_t)window);
+        std::sort(free_slots.begin(), free_slots.end());
+        for (size_t k = 0; k < free_slots.size(); ++k) col_of_slot[free_slots[k]] = (int)k;
+        const int n = st.cov_info.n_cam;
+        std::vector<int> src;      // engine column of every result column
+        for (uint32_t id = frame_id_start + n_const; id <= frame_id_end; ++id) {
+          result->covarianceFrameIds.push_back(id);
+          src.push_back(col_of_slot[id % (uint32_t)window]);
+        }
+        if (n != 6 * (int)src.size()) throw std::logic_error("pba_covariance: camera columns do not match the free frames of the window");
+        result->poseCovariance.assign((size_t)n * n, 0.0);
+        for (size_t a = 0; a < src.size(); ++a)
+          for (size_t b = 0; b < src.size(); ++b)
+            for (int i = 0; i < 6; ++i)
+              for (int j = 0; j < 6; ++j)
+                result->poseCovariance[(6 * a + i) * (size_t)n + 6 * b + j] = st.cam_cov[(6 * (size_t)src[a] + i) * n + 6 * src[b] + j];
+      }
+      result->refinedPointCovariances.resize(npts);
+      std::unordered_map<const ScenePoint*, size_t> index_of;      // point -> its index in the optimisation
+      index_of.reserve(selected.size());
+      for (size_t k = 0; k < selected.size(); ++k) index_of.emplace(selected[k], k);
+      for (size_t i = 0; i < npts; ++i) {
+        const auto it = index_of.find(points_to_remove[i].get());
+        if (it == index_of.end()) continue;      // (not part of this optimisation: the block stays zero)
+        const double* c9 = &st.point_cov[9 * it->second];
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) result->refinedPointCovariances[i](r, c) = c9[3 * r + c];
+      }
     }
   }
 }

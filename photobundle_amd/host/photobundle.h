@@ -56,6 +56,7 @@ class PhotometricBundleAdjustmentPyr;
 struct TrackOptions {
   int maxIterations = 50;
   int minPoints = 64;                 // below it the frame is not tracked
+  bool computeCovariance = false;     // pba_covariance after the alignment: the 6x6 covariance of the tracked pose
 };
 struct TrackResult {
   bool tracked = false;
@@ -63,6 +64,14 @@ struct TrackResult {
   double initialCost = -1.0, finalCost = -1.0;
   int numIterations = 0;
   std::string message;
+  // TrackOptions::computeCovariance: (J^T J)^-1 of the tracked camera, row-major 6x6, unit residual variance, in the engine's camera
+  // parameters (angle-axis and translation of the WORLD->CAMERA transform, not the frame-to-frame pose trackFrame returns); minPivot is
+  // the smallest Cholesky pivot of its unit-diagonal form, in (0, 1].  covarianceOk = false: not asked for, not tracked, or the call
+  // failed -- covarianceMessage then holds the engine's status and message (singular against refused).
+  bool covarianceOk = false;
+  std::string covarianceMessage;
+  double covariance[36] = {0};
+  double minPivot = 0.0;
 };
 
 // Same public surface as the reference class (nested Options / Result, addFrame, protected optimize); the private
@@ -127,6 +136,10 @@ class PhotometricBundleAdjustment {
     // (pba_set_cameras_anchored).  1 is the reference's behaviour (:809-813); valid values are 1 .. slidingWindowSize - 1, anything
     // else throws std::invalid_argument when the class is constructed.  trackFrame is not affected.
     int numConstantFrames = 1;
+    // covariance output (new): pba_covariance after every optimisation, into Result.  Needs a fixed gauge: numConstantFrames >= 2 or
+    // camerasConstant; with one constant frame the scale of the window is free and the normal matrix singular, so the constructor
+    // throws std::invalid_argument.  Off: the class produces what it produced without the field.
+    bool computeCovariance = false;
 
     Options() {}
     Options(const utils::ConfigFile& cf);
@@ -150,6 +163,21 @@ class PhotometricBundleAdjustment {
     double totalTime = -1.0;                        // seconds
     std::string message;
     std::vector<ceres::IterationSummary> iterationSummary;
+    // Options::computeCovariance: blocks of (J^T J)^-1 at the refined state, unit residual variance (scale by your own sigma^2).
+    // covarianceOk = false (with covarianceMessage) when the normal matrix was singular or the engine refused; the optimisation result
+    // above is not affected.  minCameraPivot / minPointPivot: smallest Cholesky pivots of the unit-diagonal blocks, in (0, 1] -- a value
+    // near rounding (1e-9 and below) means an inverse without meaning, the judgement is the caller's.
+    // poseCovariance: n x n row-major, n = 6 x covarianceFrameIds.size(), the free frames of the window in ascending frame id (empty with
+    // camerasConstant).  The parameters are the ENGINE's: angle-axis (3) and translation (3) of the WORLD->CAMERA transform of each
+    // frame, NOT the coordinates of `poses` (camera->world matrices); the conversion is the caller's.
+    // refinedPointCovariances: one 3x3 per entry of refinedPoints, same order (world coordinates); a point that was not part of the
+    // optimisation has an all-zero block.
+    bool covarianceOk = false;
+    std::string covarianceMessage;
+    double minCameraPivot = 0.0, minPointPivot = 0.0;
+    std::vector<uint32_t> covarianceFrameIds;
+    std::vector<double> poseCovariance;
+    EigenAlignedContainer_<Mat33> refinedPointCovariances;
 
     // cereal-based serialisation is dead code in the reference's default build; kept as stubs for the signatures
     struct Writer {

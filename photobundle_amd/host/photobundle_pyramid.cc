@@ -86,8 +86,11 @@ PhotometricBundleAdjustmentPyr::PhotometricBundleAdjustmentPyr(int num_levels, c
   if (num_levels <= 0) throw std::runtime_error("num_levels must be > 0");
   Calibration calib_pyr(calib);
   ImageSize size_pyr(im_size);
+  // (the covariance output belongs to the level whose Result is returned: the coarser levels only hand a pose on)
+  Options coarse(options);
+  coarse.computeCovariance = false;
   for (int i = 0; i < num_levels; ++i) {
-    _pyr.emplace_back(new PhotometricBundleAdjustment(calib_pyr, size_pyr, options));
+    _pyr.emplace_back(new PhotometricBundleAdjustment(calib_pyr, size_pyr, i == 0 ? options : coarse));
     _sizes.push_back(size_pyr);
     calib_pyr = calib_pyr.pyrDown();
     size_pyr = size_pyr.pyrDown();
@@ -156,7 +159,9 @@ Mat44 PhotometricBundleAdjustmentPyr::trackFrame(const uint8_t* image, const Mat
   TrackResult last;
   for (int i = n - 1; i >= 0; --i) {
     TrackResult tmp;
-    T = _pyr[i]->trackFrame(im[i].data(), T, options, &tmp);
+    TrackOptions level(options);
+    if (i > 0) level.computeCovariance = false;      // (only level 0's result is returned)
+    T = _pyr[i]->trackFrame(im[i].data(), T, level, &tmp);
     if (i == 0) last = tmp;
   }
   if (result) *result = last;
