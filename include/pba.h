@@ -171,11 +171,14 @@ void pba_destroy(pba_engine* e);
 
 /* ---- frames: replaces DescriptorFrame::Create + ImageGradient::compute (photobundle.cc:225-248, :126-135) --
  * `image` is the dense row-major rows x cols u8 frame addFrame() receives (photobundle.h:160).  The engine
- * builds its device plane (I, Gx, Gy bit-exactly as imgproc.cc:27-95) and keeps it in window slot `slot`. */
+ * builds its device plane (I, Gx, Gy bit-exactly as imgproc.cc:27-95) and keeps it in window slot `slot`.
+ * A frame is an input of the linearisation like the problem and the cameras: every pba_set_frame_* call (_u8, _channels_f32,
+ * _descriptor_u8, _pyr_down into `e`) drops the engine's linearisation and what was reduced from it.  The next pba_linearize /
+ * pba_covariance / pba_solve samples again; pba_step and pba_accept want a pba_linearize first (PBA_ERR_STATE otherwise). */
 int pba_set_frame_u8(pba_engine* e, int slot, const uint8_t* image);
 /* Multi-channel descriptors (pba_config.channels = C > 1): `channels` holds the C float channel images DescriptorFrame::
  * Create produces (photobundle.cc:225-248), [C][rows*cols] row-major; the engine adds every channel's own gradient
- * images (DescriptorFrame ctor :172-175, imgproc.cc:27-95). */
+ * images (DescriptorFrame ctor :172-175, imgproc.cc:27-95).  Drops the linearisation, as pba_set_frame_u8 does. */
 int pba_set_frame_channels_f32(pba_engine* e, int slot, int32_t n_channels, const float* channels);
 /* Debug/test readback of the device planes as float I, Gx, Gy (each rows*cols). */
 int pba_get_frame_planes(pba_engine* e, int slot, float* I, float* Gx, float* Gy);
@@ -192,7 +195,7 @@ int pba_sample_frame(pba_engine* e, int slot, int32_t channel, int32_t n, const 
  * Gy as float: photobundle.cc:229-235, imgproc.cc:27-95; engine created with channels = 3), _BITPLANES (census of the
  * 3x3-smoothed frame, its eight bit planes smoothed 5x5: imgproc.cc:109-245 with sigma_ct / sigma_bp of imgproc.h:44-46,
  * <= 0 skips the smoothing; channels = 8).  Bit-identical to pba_set_frame_channels_f32 fed with the host's channel images
- * (photobundle_amd/host/imgproc.h), at 1/12 .. 1/32 of the upload. */
+ * (photobundle_amd/host/imgproc.h), at 1/12 .. 1/32 of the upload.  Drops the linearisation, as pba_set_frame_u8 does. */
 enum { PBA_DESCRIPTOR_INTENSITY = 0, PBA_DESCRIPTOR_INTENSITY_AND_GRADIENT = 1, PBA_DESCRIPTOR_BITPLANES = 2 };
 int pba_set_frame_descriptor_u8(pba_engine* e, int slot, const uint8_t* image, int32_t descriptor, float sigma_ct, float sigma_bp);
 /* The channel images of a multi-channel slot back on the host, [C][rows*cols] (the layout pba_set_frame_channels_f32
@@ -203,7 +206,8 @@ int pba_get_frame_channels_f32(pba_engine* e, int slot, float* channels);
  * the next pyramid level; `e` must have been created for ((rows+1)/2, (cols+1)/2) on the same device), device to device.
  * `image_out` (nullable, (rows+1)/2 * (cols+1)/2 bytes) receives the down-sampled frame for the host front-end; the
  * call is asynchronous when it is null.  The depth map never enters the engine (it only initialises points on the host,
- * photobundle.cc:540-560), so cv::resize of the depth (:54-56) stays with the caller. */
+ * photobundle.cc:540-560), so cv::resize of the depth (:54-56) stays with the caller.  Drops the linearisation of `e` (not of
+ * `finer`), as pba_set_frame_u8 does. */
 int pba_set_frame_pyr_down(pba_engine* e, int slot, pba_engine* finer, int finer_slot, uint8_t* image_out);
 
 /* ---- device front-end (round 4): the per-frame work of PhotometricBundleAdjustment::addFrame on the frame that already sits in

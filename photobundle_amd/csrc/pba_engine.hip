@@ -7,6 +7,7 @@
 #include "pba_comm.h"
 #include "pba_handle.h"
 #include "pba_internal.h"
+#include "pba_mode_rules.h"
 #include "pba_kernels.h"
 #include "pba_frontend.h"
 #include "pba_resident.h"
@@ -131,6 +132,7 @@ struct pba_engine : pba::Handle {      // (device, stream, err, mem, events)
   int res_groups_max[2][2] = {{-1, -1}, {-1, -1}};   // [radius - 1][unit weights]: co-resident workgroups of k_resident (-1: not asked yet, 0: none)
   int res_groups_n[2][2] = {{-1, -1}, {-1, -1}};     // ... the reduced-system size that answer was given for
   int n_cus = 0, coop_launch = 0;
+  int lds_max = 0;                  // LDS bytes a workgroup may ask for (read once at pba_create; 0: unknown, nothing is refused on it)
   int64_t res_launches = 0;
   int last_driver = 0;              // 0 none, 1 resident, 2 pipelined, 3 host-stepped, 4 batched (pba_solve_driver)
   double wait_timeout_s = 120.0;    // PBA_WAIT_TIMEOUT_S: watchdog of the publication waits
@@ -247,6 +249,50 @@ int host_alloc(pba_engine* e, T** p, size_t n, T** dev_view = nullptr) {
 // the engine is in the full mode (cameras and points free) with every slot anchored: no camera column is left
 bool full_mode_all_anchored(const pba_engine* e) { return e->have_cams && e->n_free == 0 && !e->points_const && !e->cams_const; }
 
+// pba_config.flags: bit 0 keeps the reduced system for the test hooks, bits 1-2 pick a precision-sweep sampler mode (0: exact); the
+// fixed world rays of the inverse-depth variant as the kernels take them (null outside it)
+bool keep_system(const pba_engine* e) { return (e->cfg.flags & 1) != 0; }
+int sweep_mode(const pba_engine* e) { return (e->cfg.flags >> 1) & 3; }
+const double* rays_or_null(const pba_engine* e) { return e->inverse_depth ? e->d_rays : nullptr; }
+// `need` bytes of LDS against what a workgroup of this device may ask for: "[prefix]<count> <what> need ... of LDS for <use>, ..."
+int check_lds(pba_engine* e, size_t need, const char* prefix, int count, const char* what, const char* use) {
+  if (e->lds_max <= 0 || need <= (size_t)e->lds_max) return PBA_OK;
+  return fail(e, PBA_ERR_INVALID, "%s%d %s need %zu bytes of LDS for %s, the device offers %d per workgroup", prefix, count, what, need, use, e->lds_max);
+}
+
+// ---- what is derived from what: a setter names the inputs it changed, invalidate() drops the caches derived from them; no setter
+// assigns a validity flag itself ------------------------------------------------------------------------------------------------------
+enum Input : unsigned { kInProblem = 1, kInCameras = 2, kInPointParams = 4, kInPointsConst = 8, kInCamsConst = 16, kInFrame = 32 };
+// rec[k] no longer holds a Jacobian pass of point k (an input changed, or it is being overwritten): the sums reduced from it go too
+void drop_lin(pba_engine* e, int k) {
+  e->lin_valid[k] = false;
+  if (e->pose_sums_cur == k) e->pose_sums_cur = -1;
+  if (e->pts_sys_cur == k) e->pts_sys_cur = -1;
+}
+void invalidate(pba_engine* e, unsigned changed) {
+  if (changed) { drop_lin(e, 0); drop_lin(e, 1); e->have_lin = false; }      // the linearisation: every input (the sampler reads the frames)
+  if (changed & (kInProblem | kInCameras)) e->wide_ready = false;                                       // co-observation lists (wide_prepare)
+  if (changed & (kInProblem | kInPointParams | kInPointsConst)) e->pose_xyz_synced = false;             // constant points in both parities
+  if (changed & (kInProblem | kInCameras | kInCamsConst)) e->pts_cams_synced = false;                   // constant cameras in both parities
+  if (changed & (kInProblem | kInCameras | kInPointParams | kInCamsConst)) e->pts_dbg_valid = false;    // d_pts_V / d_pts_rhs
+}
+
+// The end of every pba_set_frame_*: the slot holds a frame, the sampler has a new input.  u8: d_img_stage holds the frame's u8 image (what
+// the device front-end's ZNCC reads); else there is none behind this frame
+int frame_uploaded(pba_engine* e, int slot, bool u8) {
+  e->img_stage_valid = u8;
+  e->frame_set[slot] = 1;
+  invalidate(e, kInFrame);
+  return PBA_OK;
+}
+
+// The features the engine has switched on, for mode_conflict (pba_mode_rules.h); `multi`: the caller's reading of multi-rank
+unsigned modes_present(const pba_engine* e, bool multi) {
+  return (multi ? kModeMulti : 0u) | (e->inverse_depth ? kModeInverseDepth : 0u) | (sweep_mode(e) ? kModeSweep : 0u) |
+         (e->have_cams && e->wide ? kModeWide : 0u) | (e->points_const ? kModePointsConst : 0u) | (e->cams_const ? kModeCamsConst : 0u) |
+         (e->have_cams && e->n_frames - e->n_free >= 2 ? kModeAnchors : 0u);
+}
+
 // Call-order / consistency check before any pass touches the device (include/pba.h: PBA_ERR_STATE).
 int check_ready(pba_engine* e, const char* who) {
   if (e->poisoned) return fail(e, PBA_ERR_STATE, "%s: the engine is unusable after a timed-out step (stalled stream / collective); destroy it", who);
@@ -320,7 +366,7 @@ void launch_sample(pba_engine* e, const SampleParams& sp) {
 // one kernel for back-substitution + candidate pass + step finalisation, at every patch radius; the opt-in
 // reduced-precision sampler modes (pba_config.flags bits 1-2) keep the unfused kernels
 // (wide windows run the unfused chain: the fused kernels stage kMaxFrames-entry tables)
-bool fused_capable(const pba_engine* e) { return e->fuse && ((e->cfg.flags >> 1) & 3) == 0 && !e->wide; }
+bool fused_capable(const pba_engine* e) { return e->fuse && sweep_mode(e) == 0 && !e->wide; }
 int sample_waves_for_radius(int) { return kSampleWaves; }
 
 __global__ void k_noop() {}
@@ -565,22 +611,14 @@ int wide_eliminate(pba_engine* e, int cur, int init_scale, const pba_solver_opti
   return PBA_OK;
 }
 
-// Why a wide window cannot run with what the engine has been given (nullptr: it can)
-const char* wide_refusal(const pba_engine* e) {
-  if (e->comm.multi()) return "multi-rank solves (pba_comm_*) are not built for wide windows";
-  if (e->inverse_depth) return "the inverse-depth mode (pba_set_inverse_depth) is not built for wide windows";
-  if ((e->cfg.flags >> 1) & 3) return "the precision-sweep sampler modes (pba_config.flags bits 1-2) are not built for wide windows";
-  return nullptr;
-}
-
 SampleParams make_sample_params(pba_engine* e, int which_point) {
   const int which_out = which_point;
   SampleParams sp{};
-  sp.prec = (e->cfg.flags >> 1) & 3;
+  sp.prec = sweep_mode(e);
   sp.frames = e->d_frames;
   sp.geom = e->d_geom[which_point];
   sp.xyz = e->d_xyz[which_point];
-  sp.rays = e->inverse_depth ? e->d_rays : nullptr;
+  sp.rays = rays_or_null(e);
   sp.desc = e->d_desc;
   sp.w2 = e->d_w2;
   sp.obs_point = e->d_obs_point;
@@ -632,7 +670,7 @@ unsigned long long* host_seq_dev(const pba_engine* e) { return reinterpret_cast<
 // k_schur at the engine's buffers of parity `cur`: everything but what the device decides (async_schur_params adds that)
 SchurParams schur_params(pba_engine* e, int cur, int init_scale, const pba_solver_options* o, double radius) {
   SchurParams sc{};
-  sc.xyz = e->d_xyz[cur]; sc.rays = e->inverse_depth ? e->d_rays : nullptr; sc.geom = e->d_geom[cur]; sc.rec = e->d_rec[cur]; sc.obs_point = e->d_obs_point;
+  sc.xyz = e->d_xyz[cur]; sc.rays = rays_or_null(e); sc.geom = e->d_geom[cur]; sc.rec = e->d_rec[cur]; sc.obs_point = e->d_obs_point;
   sc.obs_slot = e->d_obs_slot; sc.tile_info = e->d_tile_info; sc.lane_rec = e->d_lane_rec; sc.sp = e->d_sp;
   sc.ptrec = e->d_ptrec; sc.partial = e->d_partial; sc.rec_stride = e->rec_stride; sc.n_tiles = e->n_tiles; sc.n_frames = e->n_frames;
   sc.n_free = e->n_free; sc.n_pairs = e->n_pairs; sc.part_stride = e->part_stride; sc.init_scale = init_scale;
@@ -645,7 +683,7 @@ SolveParams solve_params(pba_engine* e, int cur, int init_scale, const pba_solve
   const int cand = 1 - cur;
   SolveParams so{};
   so.packed = e->d_packed; so.cams = e->d_cams[cur]; so.cams_cand = e->d_cams[cand]; so.delta_c = e->d_delta_c;
-  so.sc = e->d_sc; so.S_dbg = (e->cfg.flags & 1) ? e->d_S : nullptr; so.rhs_dbg = e->d_rhs; so.scal = e->d_scal; so.geom = e->d_geom[cur];
+  so.sc = e->d_sc; so.S_dbg = keep_system(e) ? e->d_S : nullptr; so.rhs_dbg = e->d_rhs; so.scal = e->d_scal; so.geom = e->d_geom[cur];
   so.n_frames = e->n_frames; so.n_free = e->n_free; so.n_pairs = e->n_pairs; so.stride = e->part_stride; so.anchor_mask = e->anchor_mask; so.tab = e->d_solve_tab;
   so.geom_cand = with_cand ? e->d_geom[cand] : nullptr;
   so.init_scale = init_scale; so.jacobi = o->jacobi_scaling; so.radius = radius; so.min_diag = o->min_lm_diagonal; so.max_diag = o->max_lm_diagonal;
@@ -809,6 +847,7 @@ int pba_create(const pba_config* cfg, pba_engine** out) {
   if (const char* sv = getenv("PBA_RES_EPOCH0")) e->res_epoch = e->res_epoch_launch = (unsigned)strtoul(sv, nullptr, 0);      // test aid: start next to the restart of the epochs
   (void)hipDeviceGetAttribute(&e->n_cus, hipDeviceAttributeMultiprocessorCount, cfg->device);
   (void)hipDeviceGetAttribute(&e->coop_launch, hipDeviceAttributeCooperativeLaunch, cfg->device);
+  if (hipDeviceGetAttribute(&e->lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, cfg->device) != hipSuccess) e->lds_max = 0;
   if ((rc = dev_alloc(e, &e->d_res_sync, kResSyncBytes / sizeof(unsigned)))) return bail(rc);
   if (hipMemsetAsync(e->d_res_sync, 0, kResSyncBytes, e->stream) != hipSuccess) return bail(PBA_ERR_HIP);
   if (const char* sv = getenv("PBA_WAIT_TIMEOUT_S")) { const double v = atof(sv); if (v > 0.0) e->wait_timeout_s = v; }
@@ -876,9 +915,7 @@ int pba_set_frame_channels_f32(pba_engine* e, int slot, int32_t n_channels, cons
   HIP_TRY(e, hipMemcpyAsync(e->d_frames_mc + (size_t)slot * n_channels * npix, channels, (size_t)n_channels * npix * sizeof(float),
                             hipMemcpyHostToDevice, e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));
-  e->img_stage_valid = false;       // no u8 image behind this frame: the device front-end's ZNCC has nothing to read
-  e->frame_set[slot] = 1;
-  return PBA_OK;
+  return frame_uploaded(e, slot, false);
 }
 
 int pba_set_frame_u8(pba_engine* e, int slot, const uint8_t* image) {
@@ -898,9 +935,7 @@ int pba_set_frame_u8(pba_engine* e, int slot, const uint8_t* image) {
   HIP_TRY(e, hipGetLastError());
   HIP_TRY(e, hipEventRecord(e->ev_img_stage, e->stream));
   e->img_stage_busy = true;
-  e->img_stage_valid = true;
-  e->frame_set[slot] = 1;
-  return PBA_OK;
+  return frame_uploaded(e, slot, true);
 }
 
 int pba_get_frame_planes(pba_engine* e, int slot, float* I, float* Gx, float* Gy) {
@@ -1026,9 +1061,7 @@ int pba_set_frame_descriptor_u8(pba_engine* e, int slot, const uint8_t* image, i
   HIP_TRY(e, hipGetLastError());
   HIP_TRY(e, hipEventRecord(e->ev_img_stage, e->stream));
   e->img_stage_busy = true;
-  e->img_stage_valid = true;
-  e->frame_set[slot] = 1;
-  return PBA_OK;
+  return frame_uploaded(e, slot, true);
 }
 
 int pba_set_frame_pyr_down(pba_engine* e, int slot, pba_engine* finer, int finer_slot, uint8_t* image_out) {
@@ -1058,9 +1091,7 @@ int pba_set_frame_pyr_down(pba_engine* e, int slot, pba_engine* finer, int finer
     HIP_TRY(e, hipMemcpyAsync(image_out, e->d_img_stage, (size_t)drows * dcols, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(e, hipStreamSynchronize(e->stream));
   }
-  e->img_stage_valid = true;
-  e->frame_set[slot] = 1;
-  return PBA_OK;
+  return frame_uploaded(e, slot, true);
 }
 
 // ---- device front-end ---------------------------------------------------------------------------------------------------
@@ -1300,24 +1331,14 @@ int pba_set_problem(pba_engine* e, int32_t n_points, const double* xyz, const do
   for (int o = 0; o < n_obs; ++o) e->slot_mask |= 1u << slot8[o];
   e->h_pt_begin = std::move(pt_begin);      // (wide_prepare; moved, not copied)
   e->h_obs_slot = std::move(slot8);
-  e->wide_ready = false;
   e->have_problem = true;
   e->inverse_depth = false;         // back to the reference's free world points until pba_set_inverse_depth says otherwise
   e->points_const = false;          // ... and to free points until pba_set_points_constant says otherwise
-  e->pose_xyz_synced = false; e->pose_sums_cur = -1;
   e->cams_const = false;            // ... and to free cameras until pba_set_cameras_constant says otherwise
-  e->pts_cams_synced = false; e->pts_sys_cur = -1; e->pts_dbg_valid = false;
-  e->have_lin = false;
-  e->lin_valid[0] = e->lin_valid[1] = false;
+  invalidate(e, kInProblem);
   return PBA_OK;
 }
 
-// Two or more anchored slots are a single-rank, exact-sampler feature (nullptr: the engine may run them)
-static const char* anchors_refusal(const pba_engine* e) {
-  if (e->comm.multi()) return "multi-rank solves (pba_comm_*) take at most one constant slot";
-  if ((e->cfg.flags >> 1) & 3) return "the precision-sweep sampler modes (pba_config.flags bits 1-2) take at most one constant slot";
-  return nullptr;
-}
 int pba_set_cameras(pba_engine* e, const double* cams6, int32_t n_frames, int32_t fixed_slot) {
   if (!e || !cams6 || n_frames < 2 || n_frames > e->cfg.max_frames || fixed_slot >= n_frames) return PBA_ERR_INVALID;
   return pba_set_cameras_anchored(e, cams6, n_frames, slot_mask_of_fixed(fixed_slot));
@@ -1331,27 +1352,22 @@ int pba_set_cameras_anchored(pba_engine* e, const double* cams6, int32_t n_frame
   if (nf == 0 && !e->points_const && !e->cams_const)
     return fail(e, PBA_ERR_INVALID, "pba_set_cameras_anchored: anchor_mask covers all %d slots: no camera is left to solve for; hold every "
                                     "camera constant with pba_set_cameras_constant", n_frames);
-  if (n_frames - nf >= 2) {
-    const char* why = anchors_refusal(e);
-    if (why) return fail(e, PBA_ERR_INVALID, "pba_set_cameras_anchored: %d constant slots: %s", n_frames - nf, why);
-  }
+  const unsigned present = modes_present(e, e->comm.multi());
+  if (const char* why = n_frames - nf >= 2 ? mode_conflict(present, kModeAnchors) : nullptr)
+    return fail(e, PBA_ERR_INVALID, "pba_set_cameras_anchored: %d constant slots: %s", n_frames - nf, why);
   PBA_ENTER(e);
   // the window shape picks the path: the narrow kernels stage kMaxFrames-slot camera tables and hold up to kWideMinFree - 1 free
   // cameras; a window with more slots or more free cameras runs the wide chain
   const bool wide = n_frames > kMaxFrames || nf >= kWideMinFree;
-  {
-    const char* why = wide ? wide_refusal(e) : nullptr;
+  int rc;
+  if (wide) {
+    const char* why = mode_conflict(present, kModeWide);
     if (why && nf >= kWideMinFree)
       return fail(e, PBA_ERR_INVALID, "pba_set_cameras: %d free cameras: %s (at most %d free cameras there)", nf, why, kWideMinFree - 1);
     if (why) return fail(e, PBA_ERR_INVALID, "pba_set_cameras: %d slots: %s (at most %d slots there)", n_frames, why, kMaxFrames);
-    if (wide) {
-      int lds_max = 0;
-      const size_t need = solve_wide_smem_bytes(6 * nf) + 1024;
-      if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, e->cfg.device) == hipSuccess && lds_max > 0 && need > (size_t)lds_max)
-        return fail(e, PBA_ERR_INVALID, "%d free cameras need %zu bytes of LDS for the reduced solve, the device offers %d per workgroup", nf, need, lds_max);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_wide), hipFuncAttributeMaxDynamicSharedMemorySize, (int)solve_wide_smem_bytes(6 * nf));
-      (void)hipGetLastError();
-    }
+    if ((rc = check_lds(e, solve_wide_smem_bytes(6 * nf) + 1024, "", nf, "free cameras", "the reduced solve"))) return rc;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_solve_wide), hipFuncAttributeMaxDynamicSharedMemorySize, (int)solve_wide_smem_bytes(6 * nf));
+    (void)hipGetLastError();
   }
   e->n_frames = n_frames;
   e->anchor_mask = anchor_mask;
@@ -1359,20 +1375,14 @@ int pba_set_cameras_anchored(pba_engine* e, const double* cams6, int32_t n_frame
   e->n_pairs = e->n_free * (e->n_free + 1) / 2;
   e->part_stride = 36 * e->n_pairs + 3 * 6 * e->n_free + 3;
   e->wide = wide;
-  e->wide_ready = false;
-  int rc;
+  invalidate(e, kInCameras);
   if (e->wide) {
     if ((rc = dev_alloc(e, &e->d_packed, (size_t)packed_stride(6 * e->n_free)))) return rc;
   } else {
     if (e->n_pairs > kTile) return fail(e, PBA_ERR_INVALID, "too many free cameras for the Schur tile (%d pairs)", e->n_pairs);
     // the reduced solve keeps the whole augmented matrix in LDS (dynamic) next to ~21 KB of static LDS: fits the 160 KB of a
     // gfx950 CU at every supported window; a device with less (gfx90a / gfx942: 64 KB) gets a clear error instead of a failed launch
-    int lds_max = 0;
-    if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, e->cfg.device) == hipSuccess && lds_max > 0) {
-      const size_t need = solve_blocked_smem_bytes(6 * e->n_free) + 22 * 1024;
-      if (need > (size_t)lds_max)
-        return fail(e, PBA_ERR_INVALID, "%d free cameras need %zu bytes of LDS for the reduced solve, the device offers %d per workgroup", e->n_free, need, lds_max);
-    }
+    if ((rc = check_lds(e, solve_blocked_smem_bytes(6 * e->n_free) + 22 * 1024, "", e->n_free, "free cameras", "the reduced solve"))) return rc;
     if ((rc = dev_alloc(e, &e->d_partial, (size_t)(256 * 4) * (((size_t)e->part_stride + 15) / 16 * 16)))) return rc;      // [entry / 16][workgroup][16]
     if ((rc = dev_alloc(e, &e->d_red, (size_t)pba_engine::kChunks * e->part_stride))) return rc;
     if ((rc = dev_alloc(e, &e->d_packed, (size_t)e->part_stride))) return rc;
@@ -1390,10 +1400,6 @@ int pba_set_cameras_anchored(pba_engine* e, const double* cams6, int32_t n_frame
   HIP_TRY(e, hipGetLastError());
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   e->have_cams = true;
-  e->have_lin = false;
-  e->lin_valid[0] = e->lin_valid[1] = false;
-  e->pose_sums_cur = -1;
-  e->pts_cams_synced = false; e->pts_sys_cur = -1; e->pts_dbg_valid = false;
   return PBA_OK;
 }
 
@@ -1423,8 +1429,8 @@ int pba_get_state(pba_engine* e, double* cams6, double* xyz) {
 int pba_set_inverse_depth(pba_engine* e, const double* rays6, const double* rho) {
   if (!e || !rays6 || !rho) return PBA_ERR_INVALID;
   if (!e->have_problem) return fail(e, PBA_ERR_STATE, "call order violated: pba_set_inverse_depth before pba_set_problem");
-  if (e->have_cams && e->wide)
-    return fail(e, PBA_ERR_INVALID, "pba_set_inverse_depth: the inverse-depth mode is not built for wide windows (%d free cameras)", e->n_free);
+  if (const char* why = mode_conflict(modes_present(e, e->comm.multi()), kModeInverseDepth))
+    return fail(e, PBA_ERR_INVALID, "pba_set_inverse_depth: %s (%d free cameras)", why, e->n_free);
   PBA_ENTER(e);
   const int n = e->n_points;
   std::vector<double> prm((size_t)3 * n, 0.0);
@@ -1439,82 +1445,41 @@ int pba_set_inverse_depth(pba_engine* e, const double* rays6, const double* rho)
   HIP_TRY(e, hipMemcpyAsync(e->d_xyz[e->cur], prm.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   e->inverse_depth = true;
-  e->have_lin = false;
-  e->lin_valid[0] = e->lin_valid[1] = false;
-  e->pose_xyz_synced = false; e->pose_sums_cur = -1;
-  e->pts_sys_cur = -1; e->pts_dbg_valid = false;
+  invalidate(e, kInPointParams);
   return PBA_OK;
 }
 
-// Why the pose-only mode cannot run with what the engine has been given (nullptr: it can)
-static const char* pose_refusal(const pba_engine* e) {
-  if (e->comm.multi()) return "multi-rank solves (pba_comm_*) are not built for the points-constant mode";
-  if ((e->cfg.flags >> 1) & 3) return "the precision-sweep sampler modes (pba_config.flags bits 1-2) are not built for the points-constant mode";
-  return nullptr;
+// pba_set_points_constant / pba_set_cameras_constant: `mine` is the mode's own switch, `other` the other mode's
+static int set_constant_mode(pba_engine* e, int32_t on, const char* who, unsigned feature, bool* mine, bool other, unsigned input) {
+  if (!e->have_problem) return fail(e, PBA_ERR_STATE, "call order violated: %s before pba_set_problem", who);
+  PBA_NOT_POISONED(e);
+  if (const char* why = on ? mode_conflict(modes_present(e, e->comm.multi()), feature) : nullptr) return fail(e, PBA_ERR_INVALID, "%s: %s", who, why);
+  if (!on && e->have_cams && e->n_free == 0 && *mine && !other)
+    return fail(e, PBA_ERR_INVALID, "%s(0): the anchor mask covers all %d slots (pba_set_cameras_anchored): no camera is left to solve "
+                                    "for; set other cameras first, or hold every camera constant with pba_set_cameras_constant", who, e->n_frames);
+  *mine = on != 0;
+  invalidate(e, input);
+  return PBA_OK;
 }
-
 int pba_set_points_constant(pba_engine* e, int32_t on) {
-  if (!e) return PBA_ERR_INVALID;
-  if (!e->have_problem) return fail(e, PBA_ERR_STATE, "call order violated: pba_set_points_constant before pba_set_problem");
-  PBA_NOT_POISONED(e);
-  if (on) {
-    const char* why = pose_refusal(e);
-    if (why) return fail(e, PBA_ERR_INVALID, "pba_set_points_constant: %s", why);
-    if (e->cams_const)
-      return fail(e, PBA_ERR_INVALID, "pba_set_points_constant: the cameras-constant mode (pba_set_cameras_constant) is on: with every block constant the program is empty");
-  }
-  if (!on && e->have_cams && e->n_free == 0 && e->points_const && !e->cams_const)
-    return fail(e, PBA_ERR_INVALID, "pba_set_points_constant(0): the anchor mask covers all %d slots (pba_set_cameras_anchored): no camera is left to solve "
-                                    "for; set other cameras first, or hold every camera constant with pba_set_cameras_constant", e->n_frames);
-  e->points_const = on != 0;
-  e->pose_xyz_synced = false; e->pose_sums_cur = -1;
-  e->have_lin = false;
-  e->lin_valid[0] = e->lin_valid[1] = false;
-  return PBA_OK;
+  return !e ? PBA_ERR_INVALID : set_constant_mode(e, on, "pba_set_points_constant", kModePointsConst, &e->points_const, e->cams_const, kInPointsConst);
 }
-
-// The constant points live in BOTH parities (the candidate pass reads the candidate parity, pba_accept flips it): a device-to-device
-// copy of the current one, byte for byte, once per problem.
-static int pose_sync_points(pba_engine* e) {
-  if (e->pose_xyz_synced) return PBA_OK;
-  HIP_TRY(e, hipMemcpyAsync(e->d_xyz[1 - e->cur], e->d_xyz[e->cur], sizeof(double) * 3 * e->n_points, hipMemcpyDeviceToDevice, e->stream));
-  e->pose_xyz_synced = true;
-  return PBA_OK;
-}
-
-// Why the structure-only mode cannot run with what the engine has been given (nullptr: it can)
-static const char* points_refusal(const pba_engine* e) {
-  if (e->points_const) return "the points-constant mode (pba_set_points_constant) is on: with every block constant the program is empty";
-  if (e->comm.multi()) return "multi-rank solves (pba_comm_*) are not built for the cameras-constant mode";
-  if ((e->cfg.flags >> 1) & 3) return "the precision-sweep sampler modes (pba_config.flags bits 1-2) are not built for the cameras-constant mode";
-  return nullptr;
-}
-
 int pba_set_cameras_constant(pba_engine* e, int32_t on) {
-  if (!e) return PBA_ERR_INVALID;
-  if (!e->have_problem) return fail(e, PBA_ERR_STATE, "call order violated: pba_set_cameras_constant before pba_set_problem");
-  PBA_NOT_POISONED(e);
-  if (on) {
-    const char* why = points_refusal(e);
-    if (why) return fail(e, PBA_ERR_INVALID, "pba_set_cameras_constant: %s", why);
-  }
-  if (!on && e->have_cams && e->n_free == 0 && e->cams_const && !e->points_const)
-    return fail(e, PBA_ERR_INVALID, "pba_set_cameras_constant(0): the anchor mask covers all %d slots (pba_set_cameras_anchored): no camera is left to solve "
-                                    "for; set other cameras first, or hold every camera constant with pba_set_cameras_constant", e->n_frames);
-  e->cams_const = on != 0;
-  e->pts_cams_synced = false; e->pts_sys_cur = -1; e->pts_dbg_valid = false;
-  e->have_lin = false;
-  e->lin_valid[0] = e->lin_valid[1] = false;
-  return PBA_OK;
+  return !e ? PBA_ERR_INVALID : set_constant_mode(e, on, "pba_set_cameras_constant", kModeCamsConst, &e->cams_const, e->points_const, kInCamsConst);
 }
 
-// The constant cameras and their geometry live in BOTH parities (the candidate pass reads the candidate parity, pba_accept flips it):
-// device-to-device copies of the current ones, byte for byte, once per problem.
-static int points_sync_cameras(pba_engine* e) {
-  if (e->pts_cams_synced) return PBA_OK;
-  HIP_TRY(e, hipMemcpyAsync(e->d_cams[1 - e->cur], e->d_cams[e->cur], sizeof(double) * 6 * e->n_frames, hipMemcpyDeviceToDevice, e->stream));
-  HIP_TRY(e, hipMemcpyAsync(e->d_geom[1 - e->cur], e->d_geom[e->cur], sizeof(CamGeom) * e->n_frames, hipMemcpyDeviceToDevice, e->stream));
-  e->pts_cams_synced = true;
+// The constant blocks live in BOTH parities (the candidate pass reads the candidate parity, pba_accept flips it): device-to-device copies
+// of the current points, or cameras and geometry, byte for byte, once per problem.
+static int sync_constant_blocks(pba_engine* e) {
+  if (e->points_const && !e->pose_xyz_synced) {
+    HIP_TRY(e, hipMemcpyAsync(e->d_xyz[1 - e->cur], e->d_xyz[e->cur], sizeof(double) * 3 * e->n_points, hipMemcpyDeviceToDevice, e->stream));
+    e->pose_xyz_synced = true;
+  }
+  if (e->cams_const && !e->pts_cams_synced) {
+    HIP_TRY(e, hipMemcpyAsync(e->d_cams[1 - e->cur], e->d_cams[e->cur], sizeof(double) * 6 * e->n_frames, hipMemcpyDeviceToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(e->d_geom[1 - e->cur], e->d_geom[e->cur], sizeof(CamGeom) * e->n_frames, hipMemcpyDeviceToDevice, e->stream));
+    e->pts_cams_synced = true;
+  }
   return PBA_OK;
 }
 
@@ -1537,11 +1502,8 @@ int pba_linearize(pba_engine* e, double* cost) {
   if (!e) return PBA_ERR_INVALID;
   { const int rc0 = check_ready(e, "pba_linearize"); if (rc0) return rc0; }
   PBA_ENTER(e);
-  if (e->points_const) { const int rcp = pose_sync_points(e); if (rcp) return rcp; }
-  if (e->cams_const) { const int rcp = points_sync_cameras(e); if (rcp) return rcp; }
-  if (!e->lin_valid[e->cur]) {
-    if (e->pose_sums_cur == e->cur) e->pose_sums_cur = -1;
-    if (e->pts_sys_cur == e->cur) e->pts_sys_cur = -1;
+  { const int rcp = sync_constant_blocks(e); if (rcp) return rcp; }
+  if (!e->lin_valid[e->cur]) {      // (whatever dropped it dropped the sums reduced from it: drop_lin)
     SampleParams sp = make_sample_params(e, e->cur);
     ev_begin(e, 0);
     launch_sample<true>(e, sp);
@@ -1638,7 +1600,7 @@ static void candidate_pass(pba_engine* e, const SampleParams& sp, int cand, bool
   ev_end(e, k);
   ++(e->speculate ? e->jac_passes : e->cost_passes);
   e->cost_blocks[cand] = fused ? e->fused_grid : e->sample_grid;
-  e->lin_valid[cand] = e->speculate;
+  drop_lin(e, cand); e->lin_valid[cand] = e->speculate;      // rec[cand] is overwritten: with a Jacobian pass when speculating
 }
 
 // pba_step of the pose-only mode (pba_pose.h): per-camera sums of the stored linearisation (once per linearisation), the block-diagonal
@@ -1647,13 +1609,13 @@ static int pose_step(pba_engine* e, double radius, int32_t init_scale, const pba
                      int grad_only) {
   const int cur = e->cur, cand = 1 - e->cur;
   int rc;
-  if ((rc = pose_sync_points(e))) return rc;
+  if ((rc = sync_constant_blocks(e))) return rc;
   if ((rc = dev_alloc(e, &e->d_pose_partial, (size_t)kPoseMaxGrid * kMaxFramesWide * kPoseVals))) return rc;
   if ((rc = dev_alloc(e, &e->d_pose_sums, (size_t)kMaxFramesWide * kPoseVals + 2))) return rc;
   const bool reduce = e->pose_sums_cur != cur;
   if (reduce) {
     PoseSystemParams ps{};
-    ps.xyz = e->d_xyz[cur]; ps.rays = e->inverse_depth ? e->d_rays : nullptr; ps.geom = e->d_geom[cur]; ps.rec = e->d_rec[cur];
+    ps.xyz = e->d_xyz[cur]; ps.rays = rays_or_null(e); ps.geom = e->d_geom[cur]; ps.rec = e->d_rec[cur];
     ps.obs_point = e->d_obs_point; ps.obs_slot = e->d_obs_slot; ps.partial = e->d_pose_partial; ps.rec_stride = e->rec_stride;
     ps.n_obs = e->n_obs; ps.n_frames = e->n_frames; ps.fx = e->cfg.fx; ps.fy = e->cfg.fy;
     e->pose_grid = std::max(1, std::min(kPoseMaxGrid, (e->n_obs + kPoseThreads - 1) / kPoseThreads));
@@ -1665,7 +1627,7 @@ static int pose_step(pba_engine* e, double radius, int32_t init_scale, const pba
   PoseSolveParams so{};
   so.partial = e->d_pose_partial; so.sums = e->d_pose_sums; so.block_cost = e->d_block_cost[cur]; so.block_fail = e->d_block_fail[cur];
   so.cams = e->d_cams[cur]; so.cams_cand = e->d_cams[cand]; so.delta_c = e->d_delta_c; so.sc = e->d_sc;
-  so.S_dbg = (e->cfg.flags & 1) ? e->d_S : nullptr; so.rhs_dbg = e->d_rhs; so.scal = e->d_scal;
+  so.S_dbg = keep_system(e) ? e->d_S : nullptr; so.rhs_dbg = e->d_rhs; so.scal = e->d_scal;
   so.geom = e->d_geom[cur]; so.geom_cand = e->d_geom[cand];
   so.n_parts = e->pose_grid; so.n_cost_blocks = e->cost_blocks[cur]; so.reduce = reduce ? 1 : 0;
   so.n_frames = e->n_frames; so.n_free = e->n_free; so.anchor_mask = e->anchor_mask; so.init_scale = init_scale; so.jacobi = o->jacobi_scaling;
@@ -1696,9 +1658,9 @@ static int points_step(pba_engine* e, double radius, int32_t init_scale, const p
                        int grad_only) {
   const int cur = e->cur, cand = 1 - e->cur;
   const int grid = (e->n_points + kPointsThreads - 1) / kPointsThreads;
-  const bool dbg = (e->cfg.flags & 1) != 0;
+  const bool dbg = keep_system(e);
   int rc;
-  if ((rc = points_sync_cameras(e))) return rc;
+  if ((rc = sync_constant_blocks(e))) return rc;
   if ((rc = dev_alloc(e, &e->d_pts_sys, (size_t)kPointsSys * e->n_points))) return rc;
   if ((rc = dev_alloc(e, &e->d_pts_part, (size_t)grid * kPointsWaves * kPointsRow))) return rc;
   if (dbg) {
@@ -1707,7 +1669,7 @@ static int points_step(pba_engine* e, double radius, int32_t init_scale, const p
   }
   if (e->pts_sys_cur != cur) {
     PointsSystemParams ps{};
-    ps.xyz = e->d_xyz[cur]; ps.rays = e->inverse_depth ? e->d_rays : nullptr; ps.geom = e->d_geom[cur]; ps.rec = e->d_rec[cur];
+    ps.xyz = e->d_xyz[cur]; ps.rays = rays_or_null(e); ps.geom = e->d_geom[cur]; ps.rec = e->d_rec[cur];
     ps.pt_begin = e->d_pt_begin; ps.obs_slot = e->d_obs_slot; ps.sys = e->d_pts_sys; ps.rec_stride = e->rec_stride;
     ps.n_points = e->n_points; ps.n_frames = e->n_frames; ps.fx = e->cfg.fx; ps.fy = e->cfg.fy;
     ev_begin(e, 2);
@@ -1742,7 +1704,7 @@ static int points_step(pba_engine* e, double radius, int32_t init_scale, const p
   if ((rc == PBA_OK || rc == PBA_ERR_NUMERIC) && !grad_only && !out->linear_solver_ok) {
     // a failed block makes the whole step a zero step: the candidate points are the current ones again
     HIP_TRY(e, hipMemcpyAsync(e->d_xyz[cand], e->d_xyz[cur], sizeof(double) * 3 * e->n_points, hipMemcpyDeviceToDevice, e->stream));
-    e->lin_valid[cand] = false;
+    drop_lin(e, cand);
   }
   return rc;
 }
@@ -1810,7 +1772,7 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
     if (sp.dbg) dump_fused_sample_timeline(e, sp.dbg);
   } else if (!grad_only) {
     BacksubParams bs{};
-    bs.xyz = e->d_xyz[cur]; bs.rays = e->inverse_depth ? e->d_rays : nullptr; bs.xyz_cand = e->d_xyz[cand]; bs.geom = e->d_geom[cur]; bs.rec = e->d_rec[cur];
+    bs.xyz = e->d_xyz[cur]; bs.rays = rays_or_null(e); bs.xyz_cand = e->d_xyz[cand]; bs.geom = e->d_geom[cur]; bs.rec = e->d_rec[cur];
     bs.pt_begin = e->d_pt_begin; bs.obs_slot = e->d_obs_slot; bs.sp = e->d_sp; bs.ptrec = e->d_ptrec;
     bs.delta_c = e->d_delta_c; bs.block_out = e->d_bs_out; bs.rec_stride = e->rec_stride; bs.n_points = e->n_points;
     bs.fx = e->cfg.fx; bs.fy = e->cfg.fy;
@@ -1838,17 +1800,15 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
 int pba_accept(pba_engine* e) {
   if (!e) return PBA_ERR_INVALID;
   if (!e->have_lin) return fail(e, PBA_ERR_STATE, "call order violated: pba_accept before pba_step");
-  e->lin_valid[e->cur] = false;
+  drop_lin(e, e->cur);      // (the sums were reduced from this parity: pose_step / points_step)
   e->cur = 1 - e->cur;
   e->have_lin = e->lin_valid[e->cur];
-  e->pose_sums_cur = -1;
-  e->pts_sys_cur = -1;
   return PBA_OK;
 }
 
 int pba_get_point_system(pba_engine* e, double* V9, double* rhs3) {
   if (!e) return PBA_ERR_INVALID;
-  if (!(e->cfg.flags & 1)) return fail(e, PBA_ERR_STATE, "call order violated: pba_get_point_system needs pba_config.flags bit 0 (keep reduced system)");
+  if (!keep_system(e)) return fail(e, PBA_ERR_STATE, "call order violated: pba_get_point_system needs pba_config.flags bit 0 (keep reduced system)");
   if (!e->cams_const || !e->pts_dbg_valid)
     return fail(e, PBA_ERR_STATE, "call order violated: pba_get_point_system needs a pba_step in the cameras-constant mode (pba_set_cameras_constant)");
   PBA_ENTER(e);
@@ -1860,7 +1820,7 @@ int pba_get_point_system(pba_engine* e, double* V9, double* rhs3) {
 
 int pba_get_reduced_system(pba_engine* e, double* S, double* rhs, int32_t* n_out) {
   if (!e || !n_out) return PBA_ERR_INVALID;
-  if (!(e->cfg.flags & 1)) return fail(e, PBA_ERR_STATE, "call order violated: pba_get_reduced_system needs pba_config.flags bit 0 (keep reduced system)");
+  if (!keep_system(e)) return fail(e, PBA_ERR_STATE, "call order violated: pba_get_reduced_system needs pba_config.flags bit 0 (keep reduced system)");
   if (e->cams_const) return fail(e, PBA_ERR_STATE, "pba_get_reduced_system: the cameras-constant mode (pba_set_cameras_constant) has no reduced camera system; see pba_get_point_system");
   PBA_ENTER(e);
   const int n = 6 * e->n_free;
@@ -1879,16 +1839,12 @@ int pba_covariance(pba_engine* e, double* cam_cov, double* point_cov, pba_covari
   inf.min_cam_pivot = 1.0; inf.min_point_pivot = 1.0; inf.failed_index = -1;
   if (info) *info = inf;
   const bool pose = e->points_const, structure = e->cams_const;
-  if (e->comm.multi()) return fail(e, PBA_ERR_INVALID, "pba_covariance: multi-rank engines (pba_comm_*) are not built for the covariance output");
-  if ((e->cfg.flags >> 1) & 3)
-    return fail(e, PBA_ERR_INVALID, "pba_covariance: the precision-sweep sampler modes (pba_config.flags bits 1-2) are not built for the covariance output");
+  const unsigned present = modes_present(e, e->comm.multi()) & ~((pose || structure) ? (unsigned)kModeInverseDepth : 0u);      // (free cameras only)
+  if (const char* why = mode_conflict(present, kModeCovariance)) return fail(e, PBA_ERR_INVALID, "pba_covariance: %s", why);
   if (pose && point_cov)
     return fail(e, PBA_ERR_INVALID, "pba_covariance: the points are constant (pba_set_points_constant): point_cov must be NULL");
   if (structure && cam_cov)
     return fail(e, PBA_ERR_INVALID, "pba_covariance: the cameras are constant (pba_set_cameras_constant): cam_cov must be NULL");
-  if (!pose && !structure && e->inverse_depth)
-    return fail(e, PBA_ERR_INVALID, "pba_covariance: the inverse-depth mode (pba_set_inverse_depth) with free cameras is not built; the "
-                                    "cameras-constant mode takes it");
   { const int rc0 = check_ready(e, "pba_covariance"); if (rc0) return rc0; }
   // the program's camera columns in ascending slot order
   CovSchurParams cs{};
@@ -1915,13 +1871,8 @@ int pba_covariance(pba_engine* e, double* cam_cov, double* point_cov, pba_covari
   const int dim = e->inverse_depth ? 1 : 3;
   const int pt_blocks = (e->n_points + kCovThreads - 1) / kCovThreads;
   PBA_ENTER(e);
-  if (n > 0) {
-    int lds_max = 0;
-    const size_t need = cov_invert_smem_bytes(n) + 64;
-    if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, e->cfg.device) == hipSuccess && lds_max > 0 && need > (size_t)lds_max)
-      return fail(e, PBA_ERR_INVALID, "pba_covariance: %d camera columns need %zu bytes of LDS for the inverse, the device offers %d per workgroup", n_cols, need, lds_max);
-  }
   int rc;
+  if (n > 0 && (rc = check_lds(e, cov_invert_smem_bytes(n) + 64, "pba_covariance: ", n_cols, "camera columns", "the inverse"))) return rc;
   if ((rc = pba_linearize(e, nullptr))) return rc;
   const int cur = e->cur;
   if ((rc = dev_alloc(e, &e->d_cov_part, (size_t)kCovPart * pt_blocks))) return rc;
@@ -1935,7 +1886,7 @@ int pba_covariance(pba_engine* e, double* cam_cov, double* point_cov, pba_covari
     if ((rc = dev_alloc(e, &e->d_cov_C, (size_t)n * n))) return rc;
     if ((rc = dev_alloc(e, &e->d_cov_info, (size_t)2))) return rc;
   }
-  const double* rays = e->inverse_depth ? e->d_rays : nullptr;
+  const double* rays = rays_or_null(e);
   CovPointParams pp{};
   pp.xyz = e->d_xyz[cur]; pp.rays = rays; pp.geom = e->d_geom[cur]; pp.rec = e->d_rec[cur]; pp.pt_begin = e->d_pt_begin; pp.obs_slot = e->d_obs_slot;
   pp.P = pose ? nullptr : e->d_cov_P; pp.X = pose ? nullptr : e->d_cov_X; pp.pp = structure ? e->d_cov_pp : nullptr; pp.part = e->d_cov_part; pp.rec_stride = e->rec_stride;
@@ -2043,16 +1994,19 @@ int pba_get_obs_records(pba_engine* e, double* rec6) {
 
 int pba_comm_unique_id(void* id128) { return Comm::unique_id(id128) ? PBA_ERR_COMM : PBA_OK; }
 
+// What both pba_comm_init_* ask first: may an engine in this state join `world` ranks?
+static int comm_init_refusal(pba_engine* e, int32_t world) {
+  unsigned with = 0;
+  const char* why = world > 1 ? mode_conflict(modes_present(e, false), kModeMulti, &with) : nullptr;
+  if (!why) return PBA_OK;
+  if (with == kModeWide) return fail(e, PBA_ERR_INVALID, "pba_comm_init: %s (%d free cameras)", why, e->n_free);
+  if (with == kModeAnchors) return fail(e, PBA_ERR_INVALID, "pba_comm_init: %s (pba_set_cameras_anchored holds %d)", why, e->n_frames - e->n_free);
+  return fail(e, PBA_ERR_INVALID, "pba_comm_init: %s", why);
+}
+
 int pba_comm_init_rccl(pba_engine* e, const void* id128, int32_t rank, int32_t world) {
   if (!e || !id128 || world < 1 || rank < 0 || rank >= world) return PBA_ERR_INVALID;
-  if (world > 1 && e->have_cams && e->wide)
-    return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for wide windows (%d free cameras)", e->n_free);
-  if (world > 1 && e->points_const)
-    return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for the points-constant mode (pba_set_points_constant)");
-  if (world > 1 && e->cams_const)
-    return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for the cameras-constant mode (pba_set_cameras_constant)");
-  if (world > 1 && e->have_cams && e->n_frames - e->n_free >= 2)
-    return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves take at most one constant slot (pba_set_cameras_anchored holds %d)", e->n_frames - e->n_free);
+  if (const int rc = comm_init_refusal(e, world)) return rc;
   PBA_ENTER(e);
   if (e->comm.init_rccl(id128, rank, world)) return fail(e, PBA_ERR_COMM, "%s", e->comm.err.c_str());
   return PBA_OK;
@@ -2060,14 +2014,7 @@ int pba_comm_init_rccl(pba_engine* e, const void* id128, int32_t rank, int32_t w
 
 int pba_comm_init_callback(pba_engine* e, pba_allreduce_fn fn, void* ctx, int32_t rank, int32_t world) {
   if (!e || !fn || world < 1 || rank < 0 || rank >= world) return PBA_ERR_INVALID;
-  if (world > 1 && e->have_cams && e->wide)
-    return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for wide windows (%d free cameras)", e->n_free);
-  if (world > 1 && e->points_const)
-    return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for the points-constant mode (pba_set_points_constant)");
-  if (world > 1 && e->cams_const)
-    return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves are not built for the cameras-constant mode (pba_set_cameras_constant)");
-  if (world > 1 && e->have_cams && e->n_frames - e->n_free >= 2)
-    return fail(e, PBA_ERR_INVALID, "pba_comm_init: multi-rank solves take at most one constant slot (pba_set_cameras_anchored holds %d)", e->n_frames - e->n_free);
+  if (const int rc = comm_init_refusal(e, world)) return rc;
   PBA_ENTER(e);
   if (e->comm.init_callback(fn, ctx, rank, world)) return fail(e, PBA_ERR_COMM, "%s", e->comm.err.c_str());
   return PBA_OK;
@@ -2438,7 +2385,7 @@ void pba_internal_resident_trace(pba_engine* e, int iterations) {
 // covers: single rank, single channel, reference-exact sampler, free world points, patch radius <= 2, <= 8 free cameras.
 int pba_internal_resident_capable(pba_engine* e, const pba_solver_options* o) {
   if (!e->use_resident || !e->use_async || !e->coop_launch || e->comm.multi() || e->channels != 1 || !fused_capable(e) || e->inverse_depth) return 0;
-  if (e->cfg.radius > 2 || e->n_free < 1 || e->n_free > kSolveNarrowFree || (e->cfg.flags & 1) || e->solve_kind != 0 || e->profile || PBA_PHASE_TIMING) return 0;
+  if (e->cfg.radius > 2 || e->n_free < 1 || e->n_free > kSolveNarrowFree || keep_system(e) || e->solve_kind != 0 || e->profile || PBA_PHASE_TIMING) return 0;
   if (o->max_num_iterations >= pba_engine::kMaxLog - 2) return 0;
   const int groups = (e->n_tiles + 1) / 2;
   if (groups > kResMaxGroups || (e->part_stride + kReduceEntries - 1) / kReduceEntries + 1 > kResMaxReduce) return 0;
@@ -2549,7 +2496,7 @@ int pba_internal_async_end(pba_engine* e) {
   { const int rcc = comm_failed(e); if (rcc) return rcc; }
   const LmState st = *e->h_lm;
   e->cur = st.cur;
-  e->lin_valid[e->cur] = true; e->lin_valid[1 - e->cur] = false;
+  drop_lin(e, 1 - e->cur); e->lin_valid[e->cur] = true;
   e->have_lin = true;
   return PBA_OK;
 }
@@ -2614,11 +2561,11 @@ int pba_internal_batch_validate(pba_engine* const* es, int32_t n, const pba_solv
     if (e->cfg.device != e0->cfg.device) return batch_refuse(es, i, PBA_ERR_INVALID, "on device %d, the batch is on device %d", e->cfg.device, e0->cfg.device);
     if (e->poisoned) return batch_refuse(es, i, PBA_ERR_STATE, "the engine is unusable after a timed-out step; destroy it");
     if (check_ready(e, "pba_solve_batch")) return batch_refuse(es, i, PBA_ERR_STATE, "%s", e->err.c_str());
-    if (e->comm.kind != 0 || e->comm.multi()) return batch_refuse(es, i, PBA_ERR_INVALID, "multi-rank engines (pba_comm_*) solve alone");
-    if (e->wide || e->n_free > kMaxFrames - 1) return batch_refuse(es, i, PBA_ERR_INVALID, "wide window (%d free cameras, a batch takes <= %d)", e->n_free, kMaxFrames - 1);
-    if ((e->cfg.flags >> 1) & 3) return batch_refuse(es, i, PBA_ERR_INVALID, "the precision-sweep flags solve alone");
-    if (e->points_const) return batch_refuse(es, i, PBA_ERR_INVALID, "the points-constant mode (pba_set_points_constant) solves alone");
-    if (e->cams_const) return batch_refuse(es, i, PBA_ERR_INVALID, "the cameras-constant mode (pba_set_cameras_constant) solves alone");
+    static_assert(kWideMinFree <= kMaxFrames, "more free cameras than a batch takes (kMaxFrames - 1) make a wide window");
+    unsigned with = 0;      // (an engine with any transport counts as multi-rank here)
+    const char* why = mode_conflict(modes_present(e, e->comm.kind != 0 || e->comm.multi()), kModeBatch, &with);
+    if (why && with == kModeWide) return batch_refuse(es, i, PBA_ERR_INVALID, "%s (%d free cameras, a batch takes <= %d)", why, e->n_free, kMaxFrames - 1);
+    if (why) return batch_refuse(es, i, PBA_ERR_INVALID, "%s", why);
     if (e->profile || e->stamps) return batch_refuse(es, i, PBA_ERR_INVALID, "profiling is on (pba_set_profiling / pba_reset_counters)");
     if (!pba_internal_async_capable(e, &o[i]) || e->solve_kind != 0)
       return batch_refuse(es, i, PBA_ERR_INVALID, "the options or the environment need the host-stepped driver (max_num_iterations %d)", o[i].max_num_iterations);
