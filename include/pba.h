@@ -374,6 +374,55 @@ typedef struct pba_covariance_info {
 } pba_covariance_info;
 int pba_covariance(pba_engine* e, double* cam_cov, double* point_cov, pba_covariance_info* info);
 
+/* ---- camera prior: what a sliding window remembers of the frames it evicted ------------------------------------
+ * ONE extra residual block on the camera blocks `slots`, with a constant Jacobian and no loss function, in information form (a
+ * marginalisation prior is singular -- it carries the gauge freedom -- so a square-root form cannot hold it).  Ceres: a CostFunction
+ * over those camera blocks with the constant Jacobian Lambda^1/2.  With d = the current cameras of `slots` minus x0:
+ *     E(d) = c + eta^T d + d^T Lambda d / 2,   gradient over the free slots eta + Lambda d,   Gauss-Newton block Lambda.
+ * k = 0 clears (the pointers may be NULL).  slots [k] ascending, each below the n_frames of the cameras that are set; x0 [k][6];
+ * Lambda [6k][6k] row-major, symmetric (the lower triangle enters the reduced system, whole rows the gradient); eta [6k]; c >= 0.
+ * An anchored slot takes part in d but has no column.  The term enters every cost the LM loop sees (the linearisation cost, the
+ * candidate cost, summary.initial_cost and final_cost, pba_linearize's cost: E is added last, after the photometric sum), the camera
+ * gradient and its norms, the column norms that fix the Jacobi scale and the LM diagonal (diag U + diag Lambda), U of the reduced
+ * system and the reduced right-hand side.  A free camera that has no residual block but is in the prior becomes a live column (it
+ * counts in x_norm).  summary.num_residual_blocks and num_residuals keep counting the PHOTOMETRIC blocks only.
+ * Also takes priors that do not come from a marginalisation (GPS / IMU, a previous covariance's inverse).
+ * Scope: the full mode on narrow windows (<= 16 slots, <= 15 free cameras), single rank, any anchor mask.  pba_solve runs the
+ * host-stepped driver while a prior is set.  Every sum has a fixed order: two fresh engines give the same bits.
+ * State: the prior is an input of the linearisation -- setting or clearing it drops the linearisation, as a pba_set_frame_* does;
+ * pba_set_cameras / pba_set_cameras_anchored clear it (a prior belongs to one set of cameras); pba_set_problem keeps it.
+ * PBA_ERR_INVALID with a message in pba_last_error, before anything is stored: the cameras are not set; k outside 0..n_frames; slots
+ * not ascending or >= n_frames; non-finite input; c < 0; multi-rank transports, the precision-sweep flags, wide windows, the
+ * points-constant and cameras-constant modes, the inverse-depth mode -- whichever call comes second; pba_covariance and pba_solve_batch
+ * refuse an engine that holds a prior.  After a refused call the engine holds what it held before. */
+int pba_set_camera_prior(pba_engine* e, int32_t k, const int32_t* slots, const double* x0, const double* Lambda, const double* eta, double c);
+
+/* The marginalisation that produces such a prior: the Schur complement, at the current (best) state, of the cameras that leave and of
+ * every point they see.  M = the points with at least one observation in a slot of drop_mask; the factors are every residual block
+ * of a point of M (in any slot) plus the engine's current prior if one is set (re-expanded at the current cameras, which is exact:
+ * priors chain from window to window); marginalised are the free dropped cameras and the points of M; kept are the free slots
+ * outside drop_mask in ascending order -- all of them, the rows of one no factor touches are exact zeros; anchored cameras are
+ * constants.  With H, g the loss-corrected Gauss-Newton matrix and gradient of those factors (no damping, no Jacobi scaling):
+ *     Lambda = H_KK - H_Km H_mm^-1 H_mK,   eta = g_K - H_Km H_mm^-1 g_m,   c = cost_M - g_m^T H_mm^-1 g_m / 2 (+ the old prior's E),
+ *     x0 = the current cameras of K (byte for byte).
+ * The points go first, through the equilibrated 3x3 Cholesky factor pba_covariance uses, then the free dropped cameras through a
+ * unit-diagonal Cholesky of their block; pivots are reported as in pba_covariance_info.  Lambda is symmetric bit for bit, every sum
+ * has a fixed order.  Outputs are sized for k = n_frames: slots [PBA_MAX_FRAMES], x0 [.][6], Lambda row-major and eta; what is written is the
+ * [6k][6k] matrix and the [6k] vector of the k that info reports (without info: the free slots outside drop_mask).
+ * The call runs pba_linearize when the current point has no valid linearisation (counted exactly as pba_covariance counts it) and
+ * moves nothing else of the LM state.  The result is what pba_set_camera_prior takes once the window has slid (the kept ring slots
+ * keep their numbers).  c can come out a rounding error below zero on a window whose marginalised blocks fit exactly.
+ * PBA_ERR_INVALID: an empty mask; bits at or above n_frames; no kept free camera; every mode the prior refuses.  PBA_ERR_NUMERIC: a
+ * non-positive or non-finite pivot -- nothing is written but info, which names the first offender (point blocks are examined first;
+ * for a camera failed_index is the row of the dropped cameras' block, 6 x its index among them + the parameter). */
+typedef struct pba_marginal_info {
+  int32_t k, n_points, n_blocks;     /* kept camera columns / 6; marginalised points; their residual blocks */
+  double  cost;                      /* loss-corrected cost of those blocks */
+  double  min_point_pivot, min_cam_pivot;   /* unit-diagonal pivots, as pba_covariance_info; 1 when there is nothing to factorise */
+  int32_t failed_is_point, failed_index;
+} pba_marginal_info;
+int pba_marginalize(pba_engine* e, uint32_t drop_mask, int32_t* slots, double* x0, double* Lambda, double* eta, double* c, pba_marginal_info* info);
+
 /* ---- several independent windows on one device ------------------------------------------------------------ */
 #define PBA_MAX_BATCH 64
 /* Solves n independent windows together: one launch of each phase of a pipelined LM iteration serves every window still running.

@@ -70,6 +70,12 @@ class CovarianceInfo(C.Structure):
                 ("failed_is_point", C.c_int32), ("failed_index", C.c_int32)]
 
 
+class MarginalInfo(C.Structure):
+    _fields_ = [("k", C.c_int32), ("n_points", C.c_int32), ("n_blocks", C.c_int32), ("cost", C.c_double),
+                ("min_point_pivot", C.c_double), ("min_cam_pivot", C.c_double),
+                ("failed_is_point", C.c_int32), ("failed_index", C.c_int32)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int64, C.c_int32, C.c_void_p)
 
 MAX_BATCH = 64     # PBA_MAX_BATCH
@@ -79,6 +85,7 @@ SYMBOLS = [
     "pba_status_string", "pba_last_error", "pba_default_solver_options", "pba_create", "pba_destroy",
     "pba_set_frame_u8", "pba_set_frame_channels_f32", "pba_get_frame_planes", "pba_get_frame_channel", "pba_sample_frame", "pba_set_frame_descriptor_u8", "pba_get_frame_channels_f32", "pba_set_frame_pyr_down", "pba_set_problem", "pba_set_cameras", "pba_set_cameras_anchored", "pba_set_inverse_depth", "pba_set_points_constant", "pba_set_cameras_constant", "pba_get_points_world", "pba_get_state",
     "pba_linearize", "pba_step", "pba_accept", "pba_get_reduced_system", "pba_get_point_system", "pba_get_obs_records", "pba_solve", "pba_solve_batch", "pba_covariance",
+    "pba_set_camera_prior", "pba_marginalize",
     "pba_comm_unique_id", "pba_comm_init_rccl", "pba_comm_init_callback", "pba_comm_enable_peer_exchange", "pba_comm_transport", "pba_comm_rank_count",
     "pba_set_profiling", "pba_get_counters", "pba_reset_counters", "pba_solve_driver",
     "pba_frontend_visibility", "pba_frontend_candidates", "pba_frontend_get_candidates", "pba_frontend_descriptors", "pba_frontend_zncc_probe",
@@ -146,6 +153,8 @@ def lib():
     L.pba_get_reduced_system.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
     L.pba_get_obs_records.argtypes = [C.c_void_p, C.c_void_p]
     L.pba_covariance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CovarianceInfo)]
+    L.pba_set_camera_prior.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double]
+    L.pba_marginalize.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(MarginalInfo)]
     L.pba_solve.argtypes = [C.c_void_p, C.POINTER(SolverOptions), C.POINTER(SolverSummary), C.c_void_p, C.c_int32]
     L.pba_solve_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     L.pba_comm_unique_id.argtypes = [C.c_void_p]

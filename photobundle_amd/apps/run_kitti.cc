@@ -81,11 +81,13 @@ static Calibration loadCalibration(const std::string& fn) {
   return calib;
 }
 
-static void dumpResult(const std::string& fn, int frame, const PhotometricBundleAdjustment::Result& r) {
+// prior: the sequence runs with marginalize = 1 (one more line, the E of the prior the optimisation carried)
+static void dumpResult(const std::string& fn, int frame, const PhotometricBundleAdjustment::Result& r, bool prior = false) {
   std::FILE* f = std::fopen(fn.c_str(), "a");
   if (!f) throw std::runtime_error("cannot open " + fn);
   std::fprintf(f, "result frame %d poses %zu points %zu iterations %zu\n", frame, r.poses.size(), r.refinedPoints.size(), r.iterationSummary.size());
   std::fprintf(f, "cost %.17g %.17g %.17g steps %d residuals %d\n", r.initialCost, r.finalCost, r.fixedCost, r.numSuccessfulStep, r.numResiduals);
+  if (prior) std::fprintf(f, "prior %.17g\n", r.priorCost);
   std::fprintf(f, "message %s\n", r.message.c_str());
   for (const auto& it : r.iterationSummary)
     std::fprintf(f, "it %d %d %d %.17g %.17g %.17g %.17g %.17g %.17g\n", it.iteration, (int)it.step_is_valid, (int)it.step_is_successful, it.cost,
@@ -261,6 +263,7 @@ int main(int argc, char** argv) {
     std::unique_ptr<PhotometricBundleAdjustmentPyr> photoba_pyr;
     if (q.num_levels > 1) photoba_pyr.reset(new PhotometricBundleAdjustmentPyr(q.num_levels, q.calib, ImageSize(rows, cols), {*q.cf}));
     else photoba.reset(new PhotometricBundleAdjustment(q.calib, ImageSize(rows, cols), {*q.cf}));
+    const bool with_prior = PhotometricBundleAdjustment::Options(*q.cf).marginalize;
     Mat44 T_last = Mat44::Identity();      // (InitialPose = track) the frame-to-frame pose the previous frame was added with
     for (int f_i = 0; (q.track || f_i < (int)q.T_init.size()) && !gStop; ++f_i) {
       if (!q.read(f_i)) break;
@@ -286,7 +289,7 @@ int main(int argc, char** argv) {
       result.initialCost = -1.0;    // the class only touches `result` when an optimisation ran (photobundle.cc:857)
       if (photoba_pyr) photoba_pyr->addFrame(q.img.data(), q.depth.data(), T, &result);
       else photoba->addFrame(q.img.data(), q.depth.data(), T, &result);
-      if (!results.empty() && result.initialCost >= 0.0) dumpResult(results, f_i, result);
+      if (!results.empty() && result.initialCost >= 0.0) dumpResult(results, f_i, result, with_prior);
     }
     writePoses(output, result, full_precision);
   } catch (const std::exception& ex) {

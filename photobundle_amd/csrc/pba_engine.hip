@@ -16,6 +16,7 @@
 #include "pba_pose.h"
 #include "pba_points.h"
 #include "pba_cov.h"
+#include "pba_prior.h"
 
 #include <algorithm>
 #include <chrono>
@@ -188,6 +189,26 @@ struct pba_engine : pba::Handle {      // (device, stream, err, mem, events)
   hipEvent_t cov_ev[2 * kCovKernels] = {}; // event profiling (pba_set_profiling(e, 1)): begin / end of each, created on first use
   double cov_ms[kCovKernels] = {0, 0, 0, 0};   // ... of the last pba_covariance, -1: the kernel did not run
 
+  // camera prior (pba_set_camera_prior, pba_prior.h): one extra residual block on the camera blocks prior_slots, in information form
+  bool prior_on = false;
+  int prior_k = 0;
+  double prior_c = 0.0;
+  int32_t prior_slots[kMaxFrames] = {};
+  double* d_prior = nullptr;        // x0 [6 k] | eta [6 k] | Lambda [6 k][6 k]
+  double* d_prior_out = nullptr;    // [6 k + 1] gradient | E of the last evaluation that asked for them
+  // marginalisation (pba_marginalize): everything on first use, nothing shared with the LM
+  double* d_marg_X = nullptr;       // [n_points][6] factor of V^-1, zero outside the marginalised points
+  double* d_marg_z = nullptr;       // [n_points][3]
+  double* d_marg_part = nullptr;    // [point blocks][kMargPart]
+  double* d_marg_S = nullptr;       // [n][n] Schur complement of the marginalised points over every free camera
+  double* d_marg_r = nullptr;       // [n] its gradient
+  double* d_marg_L = nullptr;       // [nk][nk] the output
+  double* d_marg_eta = nullptr;     // [nk]
+  double* d_marg_info = nullptr;    // [3] (k_marg_eliminate)
+  static constexpr int kMargKernels = 5;   // k_marg_point, k_marg_schur, k_marg_grad, k_prior, k_marg_eliminate
+  hipEvent_t marg_ev[2 * kMargKernels] = {};   // event profiling (pba_set_profiling(e, 1)), created on first use
+  double marg_ms[kMargKernels] = {0, 0, 0, 0, 0};   // ... of the last pba_marginalize, -1: the kernel did not run
+
   // batched solves (pba_solve_batch, pba_batch.h): the window table lives with the batch's FIRST engine (grow-only), whose stream
   // carries the batch; while a batch runs every engine's `stream` names that stream and `stream_own` keeps its own
   BatchWindow* d_batch = nullptr;
@@ -262,7 +283,7 @@ int check_lds(pba_engine* e, size_t need, const char* prefix, int count, const c
 
 // ---- what is derived from what: a setter names the inputs it changed, invalidate() drops the caches derived from them; no setter
 // assigns a validity flag itself ------------------------------------------------------------------------------------------------------
-enum Input : unsigned { kInProblem = 1, kInCameras = 2, kInPointParams = 4, kInPointsConst = 8, kInCamsConst = 16, kInFrame = 32 };
+enum Input : unsigned { kInProblem = 1, kInCameras = 2, kInPointParams = 4, kInPointsConst = 8, kInCamsConst = 16, kInFrame = 32, kInPrior = 64 };
 // rec[k] no longer holds a Jacobian pass of point k (an input changed, or it is being overwritten): the sums reduced from it go too
 void drop_lin(pba_engine* e, int k) {
   e->lin_valid[k] = false;
@@ -290,7 +311,7 @@ int frame_uploaded(pba_engine* e, int slot, bool u8) {
 unsigned modes_present(const pba_engine* e, bool multi) {
   return (multi ? kModeMulti : 0u) | (e->inverse_depth ? kModeInverseDepth : 0u) | (sweep_mode(e) ? kModeSweep : 0u) |
          (e->have_cams && e->wide ? kModeWide : 0u) | (e->points_const ? kModePointsConst : 0u) | (e->cams_const ? kModeCamsConst : 0u) |
-         (e->have_cams && e->n_frames - e->n_free >= 2 ? kModeAnchors : 0u);
+         (e->have_cams && e->n_frames - e->n_free >= 2 ? kModeAnchors : 0u) | (e->prior_on ? kModePrior : 0u);
 }
 
 // Call-order / consistency check before any pass touches the device (include/pba.h: PBA_ERR_STATE).
@@ -474,13 +495,29 @@ ReduceSolveParams reduce_solve_params(pba_engine* e, SolveParams so, int n, int 
   return rsp;
 }
 
+// The camera prior evaluated at `cams` (pba_prior.h): the caller names the destinations.  col: the reduced program's camera column of
+// every prior slot (its free index, -1 for an anchored slot, which takes part in d but has no column)
+PriorParams prior_params(const pba_engine* e, const double* cams) {
+  PriorParams pp{};
+  const int m = 6 * e->prior_k;
+  pp.x0 = e->d_prior; pp.eta = e->d_prior + m; pp.Lambda = e->d_prior + 2 * m; pp.cams = cams;
+  pp.c = e->prior_c; pp.k = e->prior_k; pp.n_free = e->n_free;
+  for (int i = 0; i < e->prior_k; ++i) {
+    pp.slot[i] = (uint8_t)e->prior_slots[i];
+    pp.col[i] = (int8_t)slot_free_index(e->anchor_mask, e->prior_slots[i]);
+  }
+  return pp;
+}
+void launch_prior(pba_engine* e, const PriorParams& pp) { hipLaunchKernelGGL(k_prior, dim3(1), dim3(kPriorThreads), 0, e->stream, pp); }
+
 int launch_reduce_and_solve(pba_engine* e, SolveParams so, int n, int cur, int cand, const LmState* lm, int final_pass, int n_cost_blocks,
                             const ReduceSolveParams::Fin* fin = nullptr) {
   const bool multi = e->comm.multi();
   const int grid = reduce_grid(e);
   const int pstride = packed_stride(n);
   const ReduceParams rp = reduce_params(e, cur, n_cost_blocks);
-  if (!multi && e->solve_kind == 0 && !(PBA_PHASE_TIMING && getenv("PBA_SPLIT_SOLVE"))) {
+  // with a camera prior the reduction and the solve stay separate launches: the prior's addend goes in between
+  if (!multi && e->solve_kind == 0 && !e->prior_on && !(PBA_PHASE_TIMING && getenv("PBA_SPLIT_SOLVE"))) {
     const ReduceSolveParams rsp = reduce_solve_params(e, so, n, cur, cand, lm, final_pass, n_cost_blocks, fin);
     ev_begin(e, 3);
     hipLaunchKernelGGL(k_reduce_solve, dim3(grid), dim3(kReduceThreads), solve_blocked_smem_bytes(n), e->stream, rsp);
@@ -515,6 +552,11 @@ int launch_reduce_and_solve(pba_engine* e, SolveParams so, int n, int cur, int c
     ev_end(e, 5);
   }
   ev_begin(e, 4);
+  if (e->prior_on) {      // (single rank: pba_set_camera_prior refuses the transports)
+    PriorParams pp = prior_params(e, so.cams);
+    pp.packed = e->d_packed;
+    launch_prior(e, pp);
+  }
   launch_solve(e, so, n);
   ev_end(e, 4);
   HIP_TRY(e, hipGetLastError());
@@ -1352,7 +1394,7 @@ int pba_set_cameras_anchored(pba_engine* e, const double* cams6, int32_t n_frame
   if (nf == 0 && !e->points_const && !e->cams_const)
     return fail(e, PBA_ERR_INVALID, "pba_set_cameras_anchored: anchor_mask covers all %d slots: no camera is left to solve for; hold every "
                                     "camera constant with pba_set_cameras_constant", n_frames);
-  const unsigned present = modes_present(e, e->comm.multi());
+  const unsigned present = modes_present(e, e->comm.multi()) & ~(unsigned)kModePrior;      // (the call clears the prior: it is in nothing's way)
   if (const char* why = n_frames - nf >= 2 ? mode_conflict(present, kModeAnchors) : nullptr)
     return fail(e, PBA_ERR_INVALID, "pba_set_cameras_anchored: %d constant slots: %s", n_frames - nf, why);
   PBA_ENTER(e);
@@ -1375,7 +1417,8 @@ int pba_set_cameras_anchored(pba_engine* e, const double* cams6, int32_t n_frame
   e->n_pairs = e->n_free * (e->n_free + 1) / 2;
   e->part_stride = 36 * e->n_pairs + 3 * 6 * e->n_free + 3;
   e->wide = wide;
-  invalidate(e, kInCameras);
+  e->prior_on = false;      // a prior belongs to one set of cameras
+  invalidate(e, kInCameras | kInPrior);
   if (e->wide) {
     if ((rc = dev_alloc(e, &e->d_packed, (size_t)packed_stride(6 * e->n_free)))) return rc;
   } else {
@@ -1498,6 +1541,17 @@ int pba_get_points_world(pba_engine* e, double* xyz) {
   return PBA_OK;
 }
 
+// E of the camera prior at the current cameras (k_prior); the gradient over the prior's rows stays in d_prior_out
+static int prior_energy(pba_engine* e, double* E) {
+  PriorParams pp = prior_params(e, e->d_cams[e->cur]);
+  pp.out = e->d_prior_out;
+  launch_prior(e, pp);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipMemcpyAsync(E, e->d_prior_out + 6 * e->prior_k, sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  return PBA_OK;
+}
+
 int pba_linearize(pba_engine* e, double* cost) {
   if (!e) return PBA_ERR_INVALID;
   { const int rc0 = check_ready(e, "pba_linearize"); if (rc0) return rc0; }
@@ -1523,6 +1577,12 @@ int pba_linearize(pba_engine* e, double* cost) {
     for (double v : bc) c += v;
     if (e->comm.multi()) {
       if (e->comm.allreduce_host(&c, 1, 0)) return fail(e, PBA_ERR_COMM, "allreduce(cost) failed: %s", e->comm.err.c_str());
+    }
+    if (e->prior_on) {      // E at the current cameras, added last
+      double E = 0.0;
+      const int rcp = prior_energy(e, &E);
+      if (rcp) return rcp;
+      c += E;
     }
     *cost = c;
   }
@@ -1761,7 +1821,7 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
     sp.tile_info = e->d_tile_info; sp.lane_rec = e->d_lane_rec; sp.geom_prev = e->d_geom[cur];
     sp.xyz_prev = e->d_xyz[cur]; sp.rec_prev = e->d_rec[cur]; sp.sp = e->d_sp; sp.ptrec = e->d_ptrec;
     sp.delta_c = e->d_delta_c; sp.block_bs = e->d_bs_out; sp.ticket = e->d_ticket; sp.scal = e->d_scal;
-    sp.host_scal = multi ? nullptr : e->h_scal_dev; sp.host_seq = h_seq_dev; sp.seq = seq; sp.n_tiles = e->n_tiles;
+    sp.host_scal = (multi || e->prior_on) ? nullptr : e->h_scal_dev; sp.host_seq = h_seq_dev; sp.seq = seq; sp.n_tiles = e->n_tiles;
     sp.dbg = (e->dbg_left > 0 && e->d_dbg) ? e->d_dbg + 8 * 1024 : nullptr;
     if (multi) {
       const int rcx = set_sample_exchange(e, sp);
@@ -1782,14 +1842,20 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
     SampleParams sp = make_sample_params(e, cand);
     candidate_pass(e, sp, cand, false);
     hipLaunchKernelGGL(k_finalize_step, dim3(1), dim3(256), 0, e->stream, e->d_bs_out, e->backsub_grid, e->d_block_cost[cand],
-                       e->d_block_fail[cand], e->sample_grid, e->d_scal, multi ? nullptr : e->h_scal_dev, h_seq_dev, seq);
+                       e->d_block_fail[cand], e->sample_grid, e->d_scal, (multi || e->prior_on) ? nullptr : e->h_scal_dev, h_seq_dev, seq);
+  }
+  if (e->prior_on && !grad_only) {
+    // the prior at the candidate cameras joins the candidate cost, last, after the photometric sum; the block is published below
+    PriorParams pp = prior_params(e, e->d_cams[cand]);
+    pp.add_to = e->d_scal + kCandCost;
+    launch_prior(e, pp);
   }
   HIP_TRY(e, hipGetLastError());
   if (multi) {
     int rc2 = exchange_step_scalars(e, xchg_packed);
     if (rc2) return rc2;
   }
-  if (multi || grad_only) {
+  if (multi || grad_only || e->prior_on) {
     hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, e->stream, e->d_scal, e->h_scal_dev, h_seq_dev, seq,
                        (const double*)(multi ? e->d_xchg : nullptr), e->comm.world);
     HIP_TRY(e, hipGetLastError());
@@ -1980,6 +2046,188 @@ void pba_internal_covariance_times(const pba_engine* e, double* ms4) {
   for (int k = 0; k < pba_engine::kCovKernels; ++k) ms4[k] = e->cov_ms[k];
 }
 
+// ---- camera prior (pba_prior.h) ---------------------------------------------------------------------------------------------------
+int pba_set_camera_prior(pba_engine* e, int32_t k, const int32_t* slots, const double* x0, const double* Lambda, const double* eta, double c) {
+  if (!e) return PBA_ERR_INVALID;
+  PBA_NOT_POISONED(e);
+  if (!e->have_cams) return fail(e, PBA_ERR_INVALID, "pba_set_camera_prior: the cameras are not set (a prior belongs to one set of cameras)");
+  if (k < 0 || k > e->n_frames) return fail(e, PBA_ERR_INVALID, "pba_set_camera_prior: k = %d is outside 0..%d", k, e->n_frames);
+  if (k == 0) {
+    e->prior_on = false;
+    e->prior_k = 0;
+    invalidate(e, kInPrior);
+    return PBA_OK;
+  }
+  if (!slots || !x0 || !Lambda || !eta) return fail(e, PBA_ERR_INVALID, "pba_set_camera_prior: null pointer with k = %d", k);
+  for (int i = 0; i < k; ++i)
+    if (slots[i] < 0 || slots[i] >= e->n_frames || (i > 0 && slots[i] <= slots[i - 1]))
+      return fail(e, PBA_ERR_INVALID, "pba_set_camera_prior: slots must ascend and stay below n_frames = %d (slots[%d] = %d)", e->n_frames, i, slots[i]);
+  const int m = 6 * k;
+  bool finite = std::isfinite(c);
+  for (int i = 0; i < m && finite; ++i) finite = std::isfinite(x0[i]) && std::isfinite(eta[i]);
+  for (size_t i = 0; i < (size_t)m * m && finite; ++i) finite = std::isfinite(Lambda[i]);
+  if (!finite) return fail(e, PBA_ERR_INVALID, "pba_set_camera_prior: non-finite input");
+  if (c < 0.0) return fail(e, PBA_ERR_INVALID, "pba_set_camera_prior: c = %g is negative", c);
+  if (const char* why = mode_conflict(modes_present(e, e->comm.multi()) & ~(unsigned)kModePrior, kModePrior))
+    return fail(e, PBA_ERR_INVALID, "pba_set_camera_prior: %s", why);
+  PBA_ENTER(e);
+  int rc;
+  // (grow-only buffers: a larger prior than the one in use moves them, so nothing of the old one is kept on a failure below -- the
+  // stream is idle here: every pass synchronises before it returns)
+  if ((rc = dev_alloc(e, &e->d_prior, (size_t)2 * m + (size_t)m * m))) return rc;
+  if ((rc = dev_alloc(e, &e->d_prior_out, (size_t)kPriorMaxDim + 1))) return rc;
+  HIP_TRY(e, hipMemcpyAsync(e->d_prior, x0, sizeof(double) * m, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(e->d_prior + m, eta, sizeof(double) * m, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(e->d_prior + 2 * m, Lambda, sizeof(double) * m * m, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  for (int i = 0; i < k; ++i) e->prior_slots[i] = slots[i];
+  e->prior_k = k;
+  e->prior_c = c;
+  e->prior_on = true;
+  invalidate(e, kInPrior);
+  return PBA_OK;
+}
+
+// Marginalisation (pba_prior.h).  Every refusal comes before the first launch; the Jacobian pass is pba_linearize's; the kernels write
+// marginalisation-owned buffers only, and the host copies the results out once every pivot is known to be positive.
+int pba_marginalize(pba_engine* e, uint32_t drop_mask, int32_t* slots, double* x0, double* Lambda, double* eta, double* c, pba_marginal_info* info) {
+  if (!e) return PBA_ERR_INVALID;
+  pba_marginal_info inf{};
+  inf.min_point_pivot = 1.0; inf.min_cam_pivot = 1.0; inf.failed_index = -1;
+  if (info) *info = inf;
+  if (!slots || !x0 || !Lambda || !eta || !c) return fail(e, PBA_ERR_INVALID, "pba_marginalize: null output pointer");
+  if (const char* why = mode_conflict(modes_present(e, e->comm.multi()) & ~(unsigned)kModePrior, kModePrior))
+    return fail(e, PBA_ERR_INVALID, "pba_marginalize: %s", why);
+  { const int rc0 = check_ready(e, "pba_marginalize"); if (rc0) return rc0; }
+  if (drop_mask == 0) return fail(e, PBA_ERR_INVALID, "pba_marginalize: drop_mask is empty");
+  if (e->n_frames < 32 && (drop_mask >> e->n_frames))
+    return fail(e, PBA_ERR_INVALID, "pba_marginalize: drop_mask 0x%x has bits at or above n_frames = %d", drop_mask, e->n_frames);
+  // camera columns of the elimination: every free slot in ascending order (the reduced program's columns), split into dropped and kept
+  MargSchurParams ms{};
+  MargEliminateParams me{};
+  int nd_cams = 0, nk_cams = 0;
+  int32_t kept_slots[kMaxFrames];
+  for (int s = 0; s < e->n_frames; ++s) {
+    const int col = slot_free_index(e->anchor_mask, s);
+    if (col < 0) continue;
+    ms.slot_of_col[col] = (uint8_t)s;
+    if ((drop_mask >> s) & 1u) me.col_d[nd_cams++] = (uint8_t)col;
+    else { kept_slots[nk_cams] = s; me.col_k[nk_cams++] = (uint8_t)col; }
+  }
+  if (nk_cams == 0) return fail(e, PBA_ERR_INVALID, "pba_marginalize: no free camera is kept (drop_mask 0x%x, anchor mask 0x%x)", drop_mask, e->anchor_mask);
+  const int n_cols = e->n_free, n = 6 * n_cols, nd = 6 * nd_cams, nk = 6 * nk_cams;
+  // the marginalised points and their residual blocks
+  for (int p = 0; p < e->n_points; ++p) {
+    bool in = false;
+    for (int o = e->h_pt_begin[p]; o < e->h_pt_begin[p + 1]; ++o) in = in || ((drop_mask >> e->h_obs_slot[o]) & 1u);
+    if (in) { ++inf.n_points; inf.n_blocks += e->h_pt_begin[p + 1] - e->h_pt_begin[p]; }
+  }
+  inf.k = nk_cams;
+  const int pt_blocks = (e->n_points + kCovThreads - 1) / kCovThreads;
+  PBA_ENTER(e);
+  int rc;
+  if ((rc = check_lds(e, marg_eliminate_smem_bytes(nd, nk) + 64, "pba_marginalize: ", nd_cams, "dropped free cameras", "their elimination"))) return rc;
+  if ((rc = pba_linearize(e, nullptr))) return rc;
+  const int cur = e->cur;
+  if ((rc = dev_alloc(e, &e->d_marg_X, (size_t)6 * e->n_points))) return rc;
+  if ((rc = dev_alloc(e, &e->d_marg_z, (size_t)3 * e->n_points))) return rc;
+  if ((rc = dev_alloc(e, &e->d_marg_part, (size_t)kMargPart * pt_blocks))) return rc;
+  if ((rc = dev_alloc(e, &e->d_marg_S, (size_t)n * n))) return rc;
+  if ((rc = dev_alloc(e, &e->d_marg_r, (size_t)n))) return rc;
+  if ((rc = dev_alloc(e, &e->d_marg_L, (size_t)nk * nk))) return rc;
+  if ((rc = dev_alloc(e, &e->d_marg_eta, (size_t)nk))) return rc;
+  if ((rc = dev_alloc(e, &e->d_marg_info, (size_t)3))) return rc;
+  const bool timed = e->profile;
+  bool ran[pba_engine::kMargKernels] = {false, false, false, false, false};
+  if (timed && !e->marg_ev[0])
+    for (int k = 0; k < 2 * pba_engine::kMargKernels; ++k) { if ((rc = handle_event(e, &e->marg_ev[k]))) return rc; }
+  auto mark = [&](int k, int end) { if (timed) { (void)hipEventRecord(e->marg_ev[2 * k + end], e->stream); ran[k] = true; } };
+  auto collect = [&]() {
+    for (int k = 0; k < pba_engine::kMargKernels; ++k) {
+      float t = 0.0f;
+      e->marg_ms[k] = (timed && ran[k] && hipEventElapsedTime(&t, e->marg_ev[2 * k], e->marg_ev[2 * k + 1]) == hipSuccess) ? (double)t : -1.0;
+    }
+  };
+  MargPointParams mp{};
+  mp.xyz = e->d_xyz[cur]; mp.geom = e->d_geom[cur]; mp.rec = e->d_rec[cur]; mp.pt_begin = e->d_pt_begin; mp.obs_slot = e->d_obs_slot;
+  mp.X = e->d_marg_X; mp.z = e->d_marg_z; mp.part = e->d_marg_part; mp.rec_stride = e->rec_stride;
+  mp.n_points = e->n_points; mp.n_frames = e->n_frames; mp.drop_mask = drop_mask; mp.fx = e->cfg.fx; mp.fy = e->cfg.fy;
+  mark(0, 0);
+  hipLaunchKernelGGL(k_marg_point, dim3(pt_blocks), dim3(kCovThreads), 0, e->stream, mp);
+  mark(0, 1);
+  ms.xyz = e->d_xyz[cur]; ms.geom = e->d_geom[cur]; ms.rec = e->d_rec[cur]; ms.pt_begin = e->d_pt_begin; ms.obs_slot = e->d_obs_slot;
+  ms.X = e->d_marg_X; ms.z = e->d_marg_z; ms.S = e->d_marg_S; ms.r = e->d_marg_r; ms.rec_stride = e->rec_stride;
+  ms.n_points = e->n_points; ms.n_cols = n_cols; ms.drop_mask = drop_mask; ms.fx = e->cfg.fx; ms.fy = e->cfg.fy;
+  mark(1, 0);
+  hipLaunchKernelGGL(k_marg_schur, dim3(n_cols * (n_cols + 1) / 2), dim3(kCovThreads), 0, e->stream, ms);
+  mark(1, 1);
+  mark(2, 0);
+  hipLaunchKernelGGL(k_marg_grad, dim3(n_cols), dim3(kCovThreads), 0, e->stream, ms);
+  mark(2, 1);
+  if (e->prior_on) {
+    // the current prior is one more factor: re-expanded at the current cameras (exact: it is quadratic), so priors chain
+    PriorParams pp = prior_params(e, e->d_cams[cur]);
+    pp.S = e->d_marg_S; pp.r = e->d_marg_r; pp.ld = n; pp.out = e->d_prior_out;
+    mark(3, 0);
+    launch_prior(e, pp);
+    mark(3, 1);
+  }
+  me.S = e->d_marg_S; me.r = e->d_marg_r; me.Lambda = e->d_marg_L; me.eta = e->d_marg_eta; me.info = e->d_marg_info;
+  me.n = n; me.nd_cams = nd_cams; me.nk_cams = nk_cams;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_marg_eliminate), hipFuncAttributeMaxDynamicSharedMemorySize, (int)marg_eliminate_smem_bytes(nd, nk));
+  (void)hipGetLastError();
+  mark(4, 0);
+  hipLaunchKernelGGL(k_marg_eliminate, dim3(1), dim3(kMargElimThreads), marg_eliminate_smem_bytes(nd, nk), e->stream, me);
+  mark(4, 1);
+  HIP_TRY(e, hipGetLastError());
+  std::vector<double> part((size_t)kMargPart * pt_blocks);
+  double einfo[3] = {1.0, -1.0, 0.0}, E_old = 0.0;
+  HIP_TRY(e, hipMemcpyAsync(part.data(), e->d_marg_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(einfo, e->d_marg_info, sizeof(einfo), hipMemcpyDeviceToHost, e->stream));
+  if (e->prior_on) HIP_TRY(e, hipMemcpyAsync(&E_old, e->d_prior_out + 6 * e->prior_k, sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  collect();
+  double cost = 0.0, zz = 0.0, bad_pt = kCovNone;
+  for (int k = 0; k < pt_blocks; ++k) {      // block order
+    inf.min_point_pivot = std::min(inf.min_point_pivot, part[(size_t)kMargPart * k]);
+    bad_pt = std::min(bad_pt, part[(size_t)kMargPart * k + 1]);
+    cost += part[(size_t)kMargPart * k + 2];
+    zz += part[(size_t)kMargPart * k + 3];
+  }
+  inf.cost = cost;
+  inf.min_cam_pivot = einfo[0];
+  if (bad_pt < kCovNone) {
+    inf.failed_is_point = 1; inf.failed_index = (int32_t)bad_pt; inf.min_point_pivot = 0.0;
+    if (info) *info = inf;
+    return fail(e, PBA_ERR_NUMERIC, "pba_marginalize: the block of point %d is not positive definite (non-positive or non-finite pivot)", inf.failed_index);
+  }
+  if (einfo[1] >= 0.0) {
+    inf.failed_is_point = 0; inf.failed_index = (int32_t)einfo[1];
+    if (info) *info = inf;
+    return fail(e, PBA_ERR_NUMERIC, "pba_marginalize: non-positive or non-finite pivot at row %d of the dropped cameras' block (slot %d, parameter %d)",
+                inf.failed_index, (int)ms.slot_of_col[me.col_d[inf.failed_index / 6]], inf.failed_index % 6);
+  }
+  // x0: the current cameras of the kept columns, byte for byte
+  std::vector<double> cams((size_t)6 * e->n_frames);
+  if ((rc = fetch_state(e, cams.data(), nullptr))) return rc;
+  HIP_TRY(e, hipMemcpyAsync(Lambda, e->d_marg_L, sizeof(double) * nk * nk, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(eta, e->d_marg_eta, sizeof(double) * nk, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  for (int i = 0; i < nk_cams; ++i) {
+    slots[i] = kept_slots[i];
+    std::memcpy(x0 + 6 * i, cams.data() + 6 * kept_slots[i], sizeof(double) * 6);
+  }
+  *c = ((cost - zz) - einfo[2]) + E_old;
+  if (info) *info = inf;
+  return PBA_OK;
+}
+
+// Event time [ms] of the five kernels of the LAST pba_marginalize (k_marg_point, k_marg_schur, k_marg_grad, k_prior, k_marg_eliminate),
+// -1 for a kernel that did not run or when event profiling (pba_set_profiling(e, 1)) was off.
+void pba_internal_marginal_times(const pba_engine* e, double* ms5) {
+  for (int k = 0; k < pba_engine::kMargKernels; ++k) ms5[k] = e->marg_ms[k];
+}
+
 int pba_get_obs_records(pba_engine* e, double* rec6) {
   if (!e || !rec6) return PBA_ERR_INVALID;
   if (!e->have_problem) return fail(e, PBA_ERR_STATE, "no problem");
@@ -2145,6 +2393,7 @@ int pba_internal_patch_len(const pba_engine* e) { return e->channels * (2 * e->c
 // ---- asynchronous driver ----------------------------------------------------------------------------------------
 int pba_internal_async_capable(const pba_engine* e, const pba_solver_options* o) {
   if (e->points_const || e->cams_const) return 0;     // the pose-only and structure-only modes are built on the host-stepped driver
+  if (e->prior_on) return 0;                          // the camera prior is an addend between reduction and solve: host-stepped only
   return e->use_async && fused_capable(e) && (e->comm.kind != 2 || e->comm.peer) && o->max_num_iterations < pba_engine::kMaxLog - 2 && !e->profile;
 }
 int pba_internal_points_constant(const pba_engine* e) { return e->points_const ? 1 : 0; }

@@ -18,6 +18,7 @@ int pba_internal_patch_len(const pba_engine* e);
 int pba_internal_points_constant(const pba_engine* e);
 int64_t pba_internal_program_blocks(const pba_engine* e);
 void pba_internal_covariance_times(const pba_engine* e, double* ms4);      // event time of the kernels of the last pba_covariance
+void pba_internal_marginal_times(const pba_engine* e, double* ms5);        // event time of the kernels of the last pba_marginalize
 double pba_internal_fixed_cost(const pba_engine* e);
 int pba_internal_refuse(pba_engine* e, int code, const char* msg);
 int pba_internal_allreduce_host(pba_engine* e, double* v, int n, int op);

@@ -11,7 +11,8 @@ namespace pba {
 
 enum ModeFeature : unsigned {      // one bit each
   kModeMulti = 1, kModeInverseDepth = 2, kModeSweep = 4 /* pba_config.flags bits 1-2 */, kModeWide = 8, kModePointsConst = 16, kModeCamsConst = 32,
-  kModeAnchors = 64 /* two or more constant slots */, kModeCovariance = 128 /* pba_covariance */, kModeBatch = 256 /* pba_solve_batch */
+  kModeAnchors = 64 /* two or more constant slots */, kModeCovariance = 128 /* pba_covariance */, kModeBatch = 256 /* pba_solve_batch */,
+  kModePrior = 512 /* pba_set_camera_prior; pba_marginalize asks as if it switched one on */
 };
 struct ModeRule { unsigned a, b; const char* then_b; const char* then_a; };
 constexpr ModeRule kModeRules[] = {
@@ -36,6 +37,17 @@ constexpr ModeRule kModeRules[] = {
     {kModeSweep, kModeBatch, "the precision-sweep flags solve alone", nullptr},
     {kModePointsConst, kModeBatch, "the points-constant mode (pba_set_points_constant) solves alone", nullptr},
     {kModeCamsConst, kModeBatch, "the cameras-constant mode (pba_set_cameras_constant) solves alone", nullptr},
+    {kModeMulti, kModePrior, "multi-rank solves (pba_comm_*) are not built for the camera prior", "multi-rank solves are not built for the camera prior (pba_set_camera_prior)"},
+    {kModePrior, kModeSweep, "the precision-sweep sampler modes (pba_config.flags bits 1-2) are not built for the camera prior", nullptr},
+    {kModePrior, kModeWide, "the camera prior (pba_set_camera_prior) is not built for wide windows", "the camera prior is not built for wide windows"},
+    {kModePointsConst, kModePrior, "the camera prior is not built for the points-constant mode (pba_set_points_constant)",
+     "the camera prior (pba_set_camera_prior) is not built for the points-constant mode"},
+    {kModeCamsConst, kModePrior, "the camera prior is not built for the cameras-constant mode (pba_set_cameras_constant)",
+     "the camera prior (pba_set_camera_prior) is not built for the cameras-constant mode"},
+    {kModeInverseDepth, kModePrior, "the camera prior is not built for the inverse-depth mode (pba_set_inverse_depth)",
+     "the camera prior (pba_set_camera_prior) is not built for the inverse-depth mode"},
+    {kModePrior, kModeCovariance, "the camera prior (pba_set_camera_prior) is set: a covariance that ignored it would be wrong", nullptr},
+    {kModePrior, kModeBatch, "the camera prior (pba_set_camera_prior) solves alone", nullptr},
 };
 
 // Why feature `on` (one bit) cannot be switched on next to the features `present` (nullptr: it can); *with: the feature in its way

@@ -321,6 +321,48 @@ class Engine:
         out["point_cov"] = pts
         return out
 
+    # ---- camera prior and marginalisation ----------------------------------------------------------------------
+    def set_camera_prior(self, slots, x0, Lambda, eta, c):
+        """pba_set_camera_prior: one extra residual block E(d) = c + eta^T d + d^T Lambda d / 2 on the camera blocks `slots`
+        (ascending), d = the cameras of `slots` minus x0 [k, 6]; Lambda [6k, 6k], eta [6k] (include/pba.h)."""
+        sl = np.ascontiguousarray(slots, np.int32).ravel()
+        k = sl.shape[0]
+        x0 = np.ascontiguousarray(x0, np.float64).reshape(k, 6)
+        Lm = np.ascontiguousarray(Lambda, np.float64).reshape(6 * k, 6 * k)
+        et = np.ascontiguousarray(eta, np.float64).reshape(6 * k)
+        self._check(self._L.pba_set_camera_prior(self._h, k, _ptr(sl), _ptr(x0), _ptr(Lm), _ptr(et), float(c)), "pba_set_camera_prior")
+
+    def clear_camera_prior(self):
+        self._check(self._L.pba_set_camera_prior(self._h, 0, None, None, None, None, 0.0), "pba_set_camera_prior")
+
+    def marginalize(self, drop_slots):
+        """pba_marginalize: the prior that the cameras of `drop_slots` and every point they see leave on the kept free cameras, at the
+        current state (include/pba.h).  Returns a dict with slots [k], x0 [k, 6], Lambda [6k, 6k], eta [6k], c and the fields of
+        pba_marginal_info -- the first five are what set_camera_prior takes.  Raises EngineError otherwise; its `status` and `info`
+        attributes carry the status code and the info fields (after PBA_ERR_NUMERIC: the first offender and the pivots)."""
+        mask = 0
+        for s in drop_slots:
+            if int(s) < 0 or int(s) >= 32:
+                raise ValueError("drop_slots: slots are 0..31, got %r" % (drop_slots,))
+            mask |= 1 << int(s)
+        info = _lib.MarginalInfo()
+        n_max = 6 * 32
+        slots = np.zeros(32, np.int32)
+        x0 = np.zeros((32, 6))
+        Lm = np.zeros(n_max * n_max)
+        eta = np.zeros(n_max)
+        c = C.c_double(0.0)
+        rc = self._L.pba_marginalize(self._h, mask, _ptr(slots), _ptr(x0), _ptr(Lm), _ptr(eta), C.byref(c), C.byref(info))
+        fields = {f: getattr(info, f) for f, _ in _lib.MarginalInfo._fields_}
+        if rc != 0:
+            err = EngineError("pba_marginalize: %s (%s)" % (self._L.pba_status_string(rc).decode(), self._L.pba_last_error(self._h).decode()))
+            err.status, err.info = rc, fields
+            raise err
+        k = info.k
+        out = dict(fields)
+        out.update(slots=slots[:k].copy(), x0=x0[:k].copy(), Lambda=Lm[:36 * k * k].reshape(6 * k, 6 * k).copy(), eta=eta[:6 * k].copy(), c=c.value)
+        return out
+
     # ---- multi-GPU -------------------------------------------------------------------------------------------
     @staticmethod
     def comm_unique_id():

@@ -172,7 +172,8 @@ PhotometricBundleAdjustment::Options::Options(const utils::ConfigFile& cf)
       device(cf.get<int>("device", 0)),
       camerasConstant((bool)cf.get<int>("camerasConstant", 0)),
       numConstantFrames(cf.get<int>("numConstantFrames", 1)),
-      computeCovariance((bool)cf.get<int>("computeCovariance", 0)) {}
+      computeCovariance((bool)cf.get<int>("computeCovariance", 0)),
+      marginalize((bool)cf.get<int>("marginalize", 0)) {}
 
 std::ostream& operator<<(std::ostream& os, const PhotometricBundleAdjustment::Options& o) {
   using DT = PhotometricBundleAdjustment::Options::DescriptorType;
@@ -183,7 +184,7 @@ std::ostream& operator<<(std::ostream& os, const PhotometricBundleAdjustment::Op
      << "\ndoGaussianWeighting = " << (o.doGaussianWeighting ? 1 : 0) << "\nrobustThreshold = " << o.robustThreshold
      << "\ndescriptorType = " << dt << "\nnumThreads = " << o.numThreads << "\nverbose = " << (o.verbose ? 1 : 0) << "\ndevice = " << o.device
      << "\ncamerasConstant = " << (o.camerasConstant ? 1 : 0) << "\nnumConstantFrames = " << o.numConstantFrames
-     << "\ncomputeCovariance = " << (o.computeCovariance ? 1 : 0) << "\n";
+     << "\ncomputeCovariance = " << (o.computeCovariance ? 1 : 0) << "\nmarginalize = " << (o.marginalize ? 1 : 0) << "\n";
   return os;
 }
 
@@ -272,6 +273,11 @@ PhotometricBundleAdjustment::PhotometricBundleAdjustment(const Calibration& cali
   if (options.computeCovariance && options.numConstantFrames < 2 && !options.camerasConstant)
     throw std::invalid_argument("computeCovariance needs numConstantFrames >= 2 or camerasConstant: with one constant frame the gauge is open (the "
                                 "scale of the window is free) and the normal matrix is singular");
+  if (options.marginalize && options.camerasConstant)
+    throw std::invalid_argument("marginalize with camerasConstant: the prior is a term on free cameras, and the cameras-constant mode has none");
+  if (options.marginalize && options.computeCovariance)
+    throw std::invalid_argument("marginalize with computeCovariance: a covariance that ignored the prior would be wrong, and the engine "
+                                "refuses it (pba_covariance)");
   // Multi-channel descriptor types: the reference's debug builds stop at `assert(p0.size() == w.size())`
   // (photobundle.cc:684: C P descriptor entries against P patch weights); its release builds run, with the weights
   // restarting per channel (:714-721), and that is what is built here.
@@ -649,6 +655,8 @@ struct PhotometricBundleAdjustment::OptimizeState {
   pba_solver_summary summary;
   std::vector<pba_iteration_summary> its;
   // Options::computeCovariance: pba_covariance at the refined state (optimizeFinish)
+  bool has_prior = false;  // Options::marginalize: the solve carried the class's prior
+  double prior_cost = 0.0;
   bool cov_ok = false;
   std::string cov_message;
   pba_covariance_info cov_info;
@@ -759,6 +767,16 @@ bool PhotometricBundleAdjustment::optimizeAssemble(OptimizeState& st) {
       st.n_anchored = n_const;
     }
     if (_options_ptr->camerasConstant) check(_engine, pba_set_cameras_constant(_engine, 1), "pba_set_cameras_constant");
+    // Options::marginalize: what the evicted frames said about these cameras, after the cameras (which clear an older prior)
+    if (_options_ptr->marginalize && _prior_valid) {
+      const int rcp = pba_set_camera_prior(_engine, (int32_t)_prior_slots.size(), _prior_slots.data(), _prior_x0.data(), _prior_Lambda.data(),
+                                           _prior_eta.data(), _prior_c);
+      if (rcp != PBA_OK) {
+        std::fprintf(stderr, "marginalisation prior dropped: pba_set_camera_prior: %s (%s)\n", pba_status_string(rcp), pba_last_error(_engine));
+        _prior_valid = false;
+      }
+      st.has_prior = _prior_valid;
+    }
     st.lap(2);
     pba_default_solver_options(&st.so);     // GetSolverOptions (:738-761)
     st.so.verbose = _options_ptr->verbose ? 1 : 0;
@@ -796,6 +814,44 @@ void PhotometricBundleAdjustment::optimizeFinish(OptimizeState& st, Result* resu
       st.cov_ok = rc == PBA_OK;
       if (!st.cov_ok) st.cov_message = std::string(pba_status_string(rc)) + " (" + pba_last_error(_engine) + ")";
     }
+    if (_options_ptr->marginalize) {
+      const int32_t first_slot = (int32_t)(frame_id_start % (uint32_t)window);
+      if (st.has_prior) {
+        // E of the prior this solve carried, at the refined cameras
+        const size_t m = 6 * _prior_slots.size();
+        std::vector<double> d(m);
+        for (size_t i = 0; i < m; ++i) d[i] = cams[6 * (size_t)_prior_slots[i / 6] + i % 6] - _prior_x0[i];
+        double E = _prior_c;
+        for (size_t i = 0; i < m; ++i) {
+          double w = 0.0;
+          for (size_t j = 0; j < m; ++j) w += _prior_Lambda[i * m + j] * d[j];
+          E += _prior_eta[i] * d[i] + 0.5 * d[i] * w;
+        }
+        st.prior_cost = E;
+      }
+      // the oldest frame leaves with its points (removePointsAtFrame below): keep what they say about the cameras that stay.  The kept
+      // ring slots keep their numbers (slot = id % window), and the slot that leaves takes the next frame
+      _prior_slots.assign(PBA_MAX_FRAMES, 0);
+      _prior_x0.assign((size_t)6 * PBA_MAX_FRAMES, 0.0);
+      _prior_Lambda.assign((size_t)36 * window * window, 0.0);
+      _prior_eta.assign((size_t)6 * window, 0.0);
+      pba_marginal_info minfo;
+      const int rcm = pba_marginalize(_engine, 1u << first_slot, _prior_slots.data(), _prior_x0.data(), _prior_Lambda.data(), _prior_eta.data(),
+                                      &_prior_c, &minfo);
+      _prior_valid = rcm == PBA_OK;
+      if (_prior_valid) {
+        _prior_slots.resize((size_t)minfo.k);
+        _prior_x0.resize((size_t)6 * minfo.k);
+        _prior_Lambda.resize((size_t)36 * minfo.k * minfo.k);
+        _prior_eta.resize((size_t)6 * minfo.k);
+        if (_prior_c < 0.0) _prior_c = 0.0;      // (a rounding error below zero when the marginalised blocks fit exactly; a constant)
+        if (_options_ptr->verbose)
+          std::fprintf(stderr, "marginalised slot %d: %d points (%d residual blocks), prior on %d cameras, pivots point %.3e camera %.3e\n",
+                       (int)first_slot, minfo.n_points, minfo.n_blocks, minfo.k, minfo.min_point_pivot, minfo.min_cam_pivot);
+      } else {
+        std::fprintf(stderr, "marginalisation failed, the prior is cleared: pba_marginalize: %s (%s)\n", pba_status_string(rcm), pba_last_error(_engine));
+      }
+    }
     // put back the refined camera poses (:841-844)
     if (!cams_const) {
       // (anchor frames did not move: their poses stay as they are -- no parameter round trip)
@@ -804,6 +860,11 @@ void PhotometricBundleAdjustment::optimizeFinish(OptimizeState& st, Result* resu
     }
   }
 
+  if (selected.empty() && _prior_valid) {
+    // nothing was solved, so nothing was marginalised: the prior belongs to a window whose oldest slot is about to be reused
+    std::fprintf(stderr, "marginalisation prior dropped: the window had no residual block\n");
+    _prior_valid = false;
+  }
   lap_o(4);
   auto points_to_remove = removePointsAtFrame(frame_id_start);
   std::printf("removing %zu old points\n", points_to_remove.size());
@@ -821,6 +882,7 @@ void PhotometricBundleAdjustment::optimizeFinish(OptimizeState& st, Result* resu
     result->initialCost = summary.initial_cost;
     result->finalCost = summary.final_cost;
     result->fixedCost = summary.fixed_cost;
+    result->priorCost = st.prior_cost;
     result->numSuccessfulStep = summary.num_successful_steps;
     result->totalTime = summary.total_time_in_seconds;
     result->numResiduals = summary.num_residuals;
@@ -890,6 +952,9 @@ void PhotometricBundleAdjustment::addFrames(const std::vector<PhotometricBundleA
     if (!instances[i] || !frames[i].T) throw std::invalid_argument("addFrames: null instance or pose");
     for (size_t j = 0; j < i; ++j) if (instances[j] == instances[i]) throw std::invalid_argument("addFrames: an instance appears twice");
   }
+  for (size_t i = 0; i < n; ++i)
+    if (instances[i]->_options_ptr->marginalize)
+      throw std::invalid_argument("addFrames: Options::marginalize solves alone (pba_solve_batch refuses an engine that holds a prior); use addFrame");
   auto result_of = [&](size_t i) { return results.empty() ? nullptr : results[i]; };
   std::vector<size_t> due;
   for (size_t i = 0; i < n; ++i)

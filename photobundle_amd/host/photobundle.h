@@ -140,6 +140,13 @@ class PhotometricBundleAdjustment {
     // camerasConstant; with one constant frame the scale of the window is free and the normal matrix singular, so the constructor
     // throws std::invalid_argument.  Off: the class produces what it produced without the field.
     bool computeCovariance = false;
+    // marginalisation prior (new): before optimize() evicts the oldest frame's points it keeps what they said about the remaining
+    // cameras as a quadratic prior (pba_marginalize on the oldest frame's ring slot), and the next window's optimisation carries it as
+    // one more residual block on those cameras (pba_set_camera_prior).  Priors chain from window to window.  Throws
+    // std::invalid_argument together with camerasConstant or computeCovariance (the constructor) and from addFrames (the batch).  A
+    // marginalisation that fails (a singular block) clears the prior, says so on stderr and does not stop the run.  Off: the class
+    // produces what it produced without the field.
+    bool marginalize = false;
 
     Options() {}
     Options(const utils::ConfigFile& cf);
@@ -158,6 +165,8 @@ class PhotometricBundleAdjustment {
     double initialCost = -1.0;
     double finalCost = -1.0;
     double fixedCost = -1.0;
+    double priorCost = 0.0;                         // Options::marginalize: E of the prior this optimisation carried, at its final state
+                                                    // (part of finalCost); 0 without a prior
     int numSuccessfulStep = 0;
     int numResiduals = 0;
     double totalTime = -1.0;                        // seconds
@@ -223,6 +232,11 @@ class PhotometricBundleAdjustment {
   // set by the pyramid class when it has already put the next frame into the engine's ring slot on the device
   // (pba_set_frame_pyr_down): addFrame() then skips its own upload
   bool _frame_resident = false;
+  // Options::marginalize: the prior the last optimisation left behind (pba_marginalize), set after the next window's cameras
+  bool _prior_valid = false;
+  std::vector<int32_t> _prior_slots;
+  std::vector<double> _prior_x0, _prior_Lambda, _prior_eta;
+  double _prior_c = 0.0;
   friend class PhotometricBundleAdjustmentPyr;
 };
 
