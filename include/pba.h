@@ -423,6 +423,56 @@ typedef struct pba_marginal_info {
 } pba_marginal_info;
 int pba_marginalize(pba_engine* e, uint32_t drop_mask, int32_t* slots, double* x0, double* Lambda, double* eta, double* c, pba_marginal_info* info);
 
+/* ---- outlier culling: the pass the reference leaves as a TODO after ceres::Solve (photobundle.cc:833-836) ---------
+ * pba_get_block_costs: c_o, the loss-corrected cost rho(|r|^2) / 2 of every residual block at the current (best) state, in the order
+ * of pba_set_problem's observation list (entry 5 of pba_get_obs_records, byte for byte).
+ * pba_cull: the verdict over those costs, and with apply != 0 the engine's problem replaced by the survivors, all on the device.
+ * The rule, with n blocks:
+ *     k = (int64) floor(quantile * (double)(n - 1));  quantile_cost = the k-th smallest c_o (0-based) in the order of the IEEE bit patterns
+ *     read as unsigned 64-bit integers (numeric order for the non-negative costs, NaN last), over ALL blocks of the problem in every mode;
+ *     threshold = factor > 0 ? fmax(min_cost, factor * quantile_cost) : min_cost;
+ *     block o is over the threshold iff !(c_o <= threshold) (a non-finite cost always is);
+ *     point p stays iff at least min_observations of its blocks are not over; otherwise all of its blocks go (n_blocks_by_point_rule counts
+ *     those that were not over themselves) and the point leaves.  Survivors keep their relative order, points and blocks alike.
+ * block_keep [n_obs before] (1: the block stays) and point_map [n_points before] (new index, or -1) are written on PBA_OK and on the
+ * "would leave no point" refusal; info whenever the verdict was reached.
+ * Both calls run pba_linearize when the current point has no valid linearisation (counted exactly as pba_covariance counts it) and move
+ * nothing else of the LM state.  apply == 0, or nothing to remove: the engine is untouched (applied = 0; a following pba_solve gives the
+ * bits it would have given without the call).
+ * An applied cull (apply != 0, at least one block removed) leaves the engine as if pba_set_problem had been called with the surviving
+ * lists and the survivors' current parameters byte for byte (in the inverse-depth mode: rho and the rays) -- except that the cameras and
+ * the anchor mask, the camera prior, the inverse-depth mode and the points-constant / cameras-constant switches stay as they are.  The
+ * linearisation is dropped as pba_set_problem drops it: pba_step wants a pba_linearize first.  Descriptors, points and rays never leave the
+ * device; the keep bytes and the point map travel to the host, which rebuilds the tile tables.
+ * Every count is an integer sum and the order statistic an exact radix select: two fresh engines give the same bytes.
+ * Narrow and wide windows, any anchor mask, inverse depth, both constant modes, an engine holding a prior, engines of pba_solve_batch.
+ * PBA_ERR_INVALID with a message in pba_last_error, before any launch, the engine unchanged: options outside their ranges; multi-rank
+ * engines; the precision-sweep flags.  After the verdict, the engine unchanged, info and the tables filled: apply != 0 and no point would
+ * be left.  PBA_ERR_NUMERIC: factor * quantile_cost is not finite (engine unchanged; info holds the counts before, quantile_cost and the
+ * non-finite product as threshold).  PBA_ERR_STATE as pba_linearize gives it. */
+int pba_get_block_costs(pba_engine* e, double* cost /* [n_obs] */);
+
+typedef struct pba_cull_options {
+  double  min_cost;          /* >= 0, finite: floor of the threshold */
+  double  factor;            /* >= 0, finite; 0: threshold = min_cost alone */
+  double  quantile;          /* in [0, 1]; read when factor > 0 */
+  int32_t min_observations;  /* >= 1: a point stays only with at least this many surviving blocks */
+  int32_t apply;             /* 0: verdict only, the engine is not changed */
+} pba_cull_options;
+
+typedef struct pba_cull_info {
+  int32_t n_blocks_before, n_blocks_after, n_points_before, n_points_after;
+  int32_t n_blocks_over_threshold;   /* removed by their own cost */
+  int32_t n_blocks_by_point_rule;    /* removed because their point fell below min_observations */
+  double  quantile_cost, threshold;
+  int32_t applied;                   /* 1 when the engine's problem was replaced */
+} pba_cull_info;
+
+int pba_cull(pba_engine* e, const pba_cull_options* o,
+             uint8_t* block_keep /* [n_obs before], nullable */,
+             int32_t* point_map  /* [n_points before]: new index or -1, nullable */,
+             pba_cull_info* info /* nullable */);
+
 /* ---- several independent windows on one device ------------------------------------------------------------ */
 #define PBA_MAX_BATCH 64
 /* Solves n independent windows together: one launch of each phase of a pipelined LM iteration serves every window still running.

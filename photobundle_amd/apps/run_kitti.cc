@@ -82,12 +82,14 @@ static Calibration loadCalibration(const std::string& fn) {
 }
 
 // prior: the sequence runs with marginalize = 1 (one more line, the E of the prior the optimisation carried)
-static void dumpResult(const std::string& fn, int frame, const PhotometricBundleAdjustment::Result& r, bool prior = false) {
+// culled: the sequence runs with outlierPasses > 0 (one more line, the residual blocks and points the optimisation's culls removed)
+static void dumpResult(const std::string& fn, int frame, const PhotometricBundleAdjustment::Result& r, bool prior = false, bool culled = false) {
   std::FILE* f = std::fopen(fn.c_str(), "a");
   if (!f) throw std::runtime_error("cannot open " + fn);
   std::fprintf(f, "result frame %d poses %zu points %zu iterations %zu\n", frame, r.poses.size(), r.refinedPoints.size(), r.iterationSummary.size());
   std::fprintf(f, "cost %.17g %.17g %.17g steps %d residuals %d\n", r.initialCost, r.finalCost, r.fixedCost, r.numSuccessfulStep, r.numResiduals);
   if (prior) std::fprintf(f, "prior %.17g\n", r.priorCost);
+  if (culled) std::fprintf(f, "culled blocks %d points %d\n", r.numCulledBlocks, r.numCulledPoints);
   std::fprintf(f, "message %s\n", r.message.c_str());
   for (const auto& it : r.iterationSummary)
     std::fprintf(f, "it %d %d %d %.17g %.17g %.17g %.17g %.17g %.17g\n", it.iteration, (int)it.step_is_valid, (int)it.step_is_successful, it.cost,
@@ -264,6 +266,10 @@ int main(int argc, char** argv) {
     if (q.num_levels > 1) photoba_pyr.reset(new PhotometricBundleAdjustmentPyr(q.num_levels, q.calib, ImageSize(rows, cols), {*q.cf}));
     else photoba.reset(new PhotometricBundleAdjustment(q.calib, ImageSize(rows, cols), {*q.cf}));
     const bool with_prior = PhotometricBundleAdjustment::Options(*q.cf).marginalize;
+    // outlierPasses > 0: optimize() culls after its solve, and so does the tracker of InitialPose = track (TrackOptions::outlierPasses)
+    const int outlier_passes = PhotometricBundleAdjustment::Options(*q.cf).outlierPasses;
+    TrackOptions track_options;
+    track_options.outlierPasses = outlier_passes;
     Mat44 T_last = Mat44::Identity();      // (InitialPose = track) the frame-to-frame pose the previous frame was added with
     for (int f_i = 0; (q.track || f_i < (int)q.T_init.size()) && !gStop; ++f_i) {
       if (!q.read(f_i)) break;
@@ -275,7 +281,7 @@ int main(int argc, char** argv) {
         const size_t m = result.poses.size();
         const Mat44 T_pred = m >= 2 ? Mat44(result.poses[m - 1].inverse() * result.poses[m - 2]) : T_last;
         TrackResult tr;
-        T = photoba_pyr ? photoba_pyr->trackFrame(q.img.data(), T_pred, TrackOptions(), &tr) : photoba->trackFrame(q.img.data(), T_pred, TrackOptions(), &tr);
+        T = photoba_pyr ? photoba_pyr->trackFrame(q.img.data(), T_pred, track_options, &tr) : photoba->trackFrame(q.img.data(), T_pred, track_options, &tr);
         if (!tr.tracked) {
           std::fprintf(stderr, "frame %d was not tracked (%s): keeping the constant-velocity prediction\n", f_i, tr.message.c_str());
           T = T_pred;
@@ -284,12 +290,13 @@ int main(int argc, char** argv) {
                     tr.initialCost, tr.finalCost);
         for (int a = 0; a < 3; ++a) for (int b = 0; b < 4; ++b) std::printf(" %.17g", T(a, b));
         std::printf("\n");
+        if (outlier_passes > 0) std::printf("track frame %d culled blocks %d points %d\n", f_i, tr.numCulledBlocks, tr.numCulledPoints);
       }
       T_last = T;
       result.initialCost = -1.0;    // the class only touches `result` when an optimisation ran (photobundle.cc:857)
       if (photoba_pyr) photoba_pyr->addFrame(q.img.data(), q.depth.data(), T, &result);
       else photoba->addFrame(q.img.data(), q.depth.data(), T, &result);
-      if (!results.empty() && result.initialCost >= 0.0) dumpResult(results, f_i, result, with_prior);
+      if (!results.empty() && result.initialCost >= 0.0) dumpResult(results, f_i, result, with_prior, outlier_passes > 0);
     }
     writePoses(output, result, full_precision);
   } catch (const std::exception& ex) {

@@ -41,6 +41,15 @@ class Allocations {
     free_entry(it->first, it->second);
     entries_.erase(it);
   }
+  // Exchanges the buffers behind two fields of the same kind (a buffer filled on the side takes the place of the one it was filled
+  // from); each field keeps the other's size.  Both must have been reserved.
+  template <class T>
+  void exchange(T** a, T** b) {
+    auto ia = entries_.find(reinterpret_cast<void**>(a)), ib = entries_.find(reinterpret_cast<void**>(b));
+    if (ia == entries_.end() || ib == entries_.end() || ia->second.kind != ib->second.kind) return;
+    T* t = *a; *a = *b; *b = t;
+    const size_t n = ia->second.bytes; ia->second.bytes = ib->second.bytes; ib->second.bytes = n;
+  }
   void release_all() {
     for (auto& kv : entries_) free_entry(kv.first, kv.second);
     entries_.clear();

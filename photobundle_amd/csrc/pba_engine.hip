@@ -17,6 +17,7 @@
 #include "pba_points.h"
 #include "pba_cov.h"
 #include "pba_prior.h"
+#include "pba_cull.h"
 
 #include <algorithm>
 #include <chrono>
@@ -208,6 +209,22 @@ struct pba_engine : pba::Handle {      // (device, stream, err, mem, events)
   static constexpr int kMargKernels = 5;   // k_marg_point, k_marg_schur, k_marg_grad, k_prior, k_marg_eliminate
   hipEvent_t marg_ev[2 * kMargKernels] = {};   // event profiling (pba_set_profiling(e, 1)), created on first use
   double marg_ms[kMargKernels] = {0, 0, 0, 0, 0};   // ... of the last pba_marginalize, -1: the kernel did not run
+
+  // outlier culling (pba_cull, pba_cull.h): everything on first use, nothing shared with the LM
+  uint32_t* d_cull_hist = nullptr;  // [kCullPasses][kCullBins] radix-select tables
+  uint64_t* d_cull_sel = nullptr;   // [kCullSelWords] (k_cull_finish)
+  int32_t* d_cull_pt_cnt = nullptr; // [n_points] surviving blocks per point
+  int4* d_cull_part = nullptr;      // [point blocks] workgroup sums
+  int2* d_cull_off = nullptr;       // [point blocks] their exclusive scan
+  int32_t* d_cull_tot = nullptr;    // [kCullTotals]
+  int32_t* d_cull_map = nullptr;    // [n_points] new index or -1
+  int32_t* d_cull_dst = nullptr;    // [n_obs] new index or -1
+  uint8_t* d_cull_keep = nullptr;   // [n_obs]
+  double* d_cull_xyz = nullptr;     // the fresh buffers the survivors are gathered into; an applied cull exchanges them with
+  float* d_cull_desc = nullptr;     // d_xyz[cur], d_desc, d_rays, d_obs_point, d_obs_slot
+  double* d_cull_rays = nullptr;
+  int32_t* d_cull_obs_point = nullptr;
+  uint8_t* d_cull_obs_slot = nullptr;
 
   // batched solves (pba_solve_batch, pba_batch.h): the window table lives with the batch's FIRST engine (grow-only), whose stream
   // carries the batch; while a batch runs every engine's `stream` names that stream and `stream_own` keeps its own
@@ -1278,15 +1295,19 @@ int pba_frontend_descriptors(pba_engine* e, int32_t slot, int32_t n, const int32
   return PBA_OK;
 }
 
-int pba_set_problem(pba_engine* e, int32_t n_points, const double* xyz, const double* desc, int32_t n_obs,
-                    const int32_t* obs_point, const int32_t* obs_slot, const double* weights) {
-  if (!e || n_points <= 0 || n_obs <= 0 || !xyz || !desc || !obs_point || !obs_slot || !weights) return PBA_ERR_INVALID;
-  PBA_ENTER(e);
-  const int P = (2 * e->cfg.radius + 1) * (2 * e->cfg.radius + 1);     // pixels of one patch (weights)
-  const int PD = P * e->channels;                                       // descriptor entries per point
-  // validate + CSR + tiles (whole points per tile of <= kTile observations)
-  std::vector<int32_t> pt_begin(n_points + 1, 0);
-  std::vector<uint8_t> slot8(n_obs);
+// The part of a problem that follows from its observation lists alone, shared by pba_set_problem and an applied pba_cull.
+struct ProblemLayout {
+  std::vector<int32_t> pt_begin;
+  std::vector<uint8_t> slot8;
+  std::vector<int4> tinfo;
+  std::vector<int2> lane_rec;
+};
+// validate + CSR + tiles (whole points per tile of <= kTile observations); sets n_tiles, n_points, n_obs
+static int problem_layout(pba_engine* e, int32_t n_points, int32_t n_obs, const int32_t* obs_point, const int32_t* obs_slot, ProblemLayout* L) {
+  std::vector<int32_t>& pt_begin = L->pt_begin;
+  std::vector<uint8_t>& slot8 = L->slot8;
+  pt_begin.assign((size_t)n_points + 1, 0);
+  slot8.resize(n_obs);
   for (int o = 0; o < n_obs; ++o) {
     const int p = obs_point[o], s = obs_slot[o];
     if (p < 0 || p >= n_points || s < 0 || s >= e->cfg.max_frames) return fail(e, PBA_ERR_INVALID, "observation %d out of range", o);
@@ -1308,35 +1329,32 @@ int pba_set_problem(pba_engine* e, int32_t n_points, const double* xyz, const do
     tiles.push_back(n_obs);
   }
   e->n_tiles = (int)tiles.size() - 1;
-  std::vector<int4> tinfo(e->n_tiles);
-  std::vector<int2> lane_rec((size_t)e->n_tiles * kTile, make_int2(0, 0));
+  L->tinfo.resize(e->n_tiles);
+  L->lane_rec.assign((size_t)e->n_tiles * kTile, make_int2(0, 0));
   for (int t = 0; t < e->n_tiles; ++t) {
     const int o0 = tiles[t], o1 = tiles[t + 1];
-    tinfo[t] = make_int4(o0, o1 - o0, obs_point[o0], obs_point[o1 - 1] - obs_point[o0] + 1);
+    L->tinfo[t] = make_int4(o0, o1 - o0, obs_point[o0], obs_point[o1 - 1] - obs_point[o0] + 1);
     for (int o = o0; o < o1; ++o) {
       const int p = obs_point[o];
-      lane_rec[(size_t)t * kTile + (o - o0)] = make_int2(p, (int)slot8[o] | ((pt_begin[p] - o0) << 8) | ((pt_begin[p + 1] - pt_begin[p]) << 16));
+      L->lane_rec[(size_t)t * kTile + (o - o0)] = make_int2(p, (int)slot8[o] | ((pt_begin[p] - o0) << 8) | ((pt_begin[p + 1] - pt_begin[p]) << 16));
     }
   }
   e->n_points = n_points;
   e->n_obs = n_obs;
   e->ctr.n_obs = n_obs; e->ctr.n_points = n_points;
-
-  std::vector<float> descf((size_t)n_points * PD);
-  for (size_t i = 0; i < descf.size(); ++i) descf[i] = (float)desc[i];
-  std::vector<double> w2(P);
-  e->unit_weights = true;
-  for (int i = 0; i < P; ++i) { w2[i] = weights[i] * weights[i]; if (weights[i] != 1.0) e->unit_weights = false; }
-
+  return PBA_OK;
+}
+// every buffer and launch shape sized by n_points / n_obs / n_tiles (PD: descriptor entries per point)
+static int problem_reserve(pba_engine* e, const ProblemLayout& L, int PD) {
+  const int n_points = e->n_points, n_obs = e->n_obs;
   int rc;
   for (int k = 0; k < 2; ++k) if ((rc = dev_alloc(e, &e->d_xyz[k], (size_t)3 * n_points))) return rc;
-  if ((rc = dev_alloc(e, &e->d_desc, descf.size()))) return rc;
-  if ((rc = dev_alloc(e, &e->d_w2, (size_t)P))) return rc;
+  if ((rc = dev_alloc(e, &e->d_desc, (size_t)n_points * PD))) return rc;
   if ((rc = dev_alloc(e, &e->d_obs_point, (size_t)n_obs))) return rc;
   if ((rc = dev_alloc(e, &e->d_obs_slot, (size_t)n_obs))) return rc;
   if ((rc = dev_alloc(e, &e->d_pt_begin, (size_t)n_points + 1))) return rc;
-  if ((rc = dev_alloc(e, &e->d_tile_info, tinfo.size()))) return rc;
-  if ((rc = dev_alloc(e, &e->d_lane_rec, lane_rec.size()))) return rc;
+  if ((rc = dev_alloc(e, &e->d_tile_info, L.tinfo.size()))) return rc;
+  if ((rc = dev_alloc(e, &e->d_lane_rec, L.lane_rec.size()))) return rc;
   e->rec_stride = ((int64_t)n_obs + 255) / 256 * 256;
   for (int k = 0; k < 2; ++k) if ((rc = dev_alloc(e, &e->d_rec[k], (size_t)6 * e->rec_stride))) return rc;
   if ((rc = dev_alloc(e, &e->d_sp, (size_t)3 * n_points))) return rc;
@@ -1357,6 +1375,42 @@ int pba_set_problem(pba_engine* e, int32_t n_points, const double* xyz, const do
   e->schur_grid = std::min(e->n_tiles, 256 * 4);
   // (experiment switch: workgroups of the persistent k_schur launch; the partial buffers are sized for <= 1024)
   if (const char* sv = getenv("PBA_SCHUR_GRID")) { const int g = atoi(sv); if (g >= 1 && g <= 1024) e->schur_grid = std::min(e->n_tiles, g); }
+  return PBA_OK;
+}
+// the index tables the host built, enqueued (the caller synchronises before L goes out of scope)
+static int problem_upload_tables(pba_engine* e, const ProblemLayout& L) {
+  HIP_TRY(e, hipMemcpyAsync(e->d_pt_begin, L.pt_begin.data(), sizeof(int32_t) * (e->n_points + 1), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(e->d_tile_info, L.tinfo.data(), sizeof(int4) * L.tinfo.size(), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(e->d_lane_rec, L.lane_rec.data(), sizeof(int2) * L.lane_rec.size(), hipMemcpyHostToDevice, e->stream));
+  return PBA_OK;
+}
+// after the synchronisation: the slot mask and the host copies of the observation structure (the caller invalidates with kInProblem)
+static void problem_installed(pba_engine* e, ProblemLayout* L) {
+  e->slot_mask = 0;
+  for (int o = 0; o < e->n_obs; ++o) e->slot_mask |= 1u << L->slot8[o];
+  e->h_pt_begin = std::move(L->pt_begin);      // (wide_prepare; moved, not copied)
+  e->h_obs_slot = std::move(L->slot8);
+  e->have_problem = true;
+}
+
+int pba_set_problem(pba_engine* e, int32_t n_points, const double* xyz, const double* desc, int32_t n_obs,
+                    const int32_t* obs_point, const int32_t* obs_slot, const double* weights) {
+  if (!e || n_points <= 0 || n_obs <= 0 || !xyz || !desc || !obs_point || !obs_slot || !weights) return PBA_ERR_INVALID;
+  PBA_ENTER(e);
+  const int P = (2 * e->cfg.radius + 1) * (2 * e->cfg.radius + 1);     // pixels of one patch (weights)
+  const int PD = P * e->channels;                                       // descriptor entries per point
+  ProblemLayout L;
+  int rc;
+  if ((rc = problem_layout(e, n_points, n_obs, obs_point, obs_slot, &L))) return rc;
+
+  std::vector<float> descf((size_t)n_points * PD);
+  for (size_t i = 0; i < descf.size(); ++i) descf[i] = (float)desc[i];
+  std::vector<double> w2(P);
+  e->unit_weights = true;
+  for (int i = 0; i < P; ++i) { w2[i] = weights[i] * weights[i]; if (weights[i] != 1.0) e->unit_weights = false; }
+
+  if ((rc = dev_alloc(e, &e->d_w2, (size_t)P))) return rc;
+  if ((rc = problem_reserve(e, L, PD))) return rc;
 
   // the points go to the CURRENT parity: the cameras of an earlier pba_set_cameras live there too, so the two calls may
   // come in either order
@@ -1364,16 +1418,10 @@ int pba_set_problem(pba_engine* e, int32_t n_points, const double* xyz, const do
   HIP_TRY(e, hipMemcpyAsync(e->d_desc, descf.data(), sizeof(float) * descf.size(), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(e, hipMemcpyAsync(e->d_w2, w2.data(), sizeof(double) * P, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(e, hipMemcpyAsync(e->d_obs_point, obs_point, sizeof(int32_t) * n_obs, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(e, hipMemcpyAsync(e->d_obs_slot, slot8.data(), n_obs, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(e, hipMemcpyAsync(e->d_pt_begin, pt_begin.data(), sizeof(int32_t) * (n_points + 1), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(e, hipMemcpyAsync(e->d_tile_info, tinfo.data(), sizeof(int4) * tinfo.size(), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(e, hipMemcpyAsync(e->d_lane_rec, lane_rec.data(), sizeof(int2) * lane_rec.size(), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(e->d_obs_slot, L.slot8.data(), n_obs, hipMemcpyHostToDevice, e->stream));
+  if ((rc = problem_upload_tables(e, L))) return rc;
   HIP_TRY(e, hipStreamSynchronize(e->stream));
-  e->slot_mask = 0;
-  for (int o = 0; o < n_obs; ++o) e->slot_mask |= 1u << slot8[o];
-  e->h_pt_begin = std::move(pt_begin);      // (wide_prepare; moved, not copied)
-  e->h_obs_slot = std::move(slot8);
-  e->have_problem = true;
+  problem_installed(e, &L);
   e->inverse_depth = false;         // back to the reference's free world points until pba_set_inverse_depth says otherwise
   e->points_const = false;          // ... and to free points until pba_set_points_constant says otherwise
   e->cams_const = false;            // ... and to free cameras until pba_set_cameras_constant says otherwise
@@ -2226,6 +2274,148 @@ int pba_marginalize(pba_engine* e, uint32_t drop_mask, int32_t* slots, double* x
 // -1 for a kernel that did not run or when event profiling (pba_set_profiling(e, 1)) was off.
 void pba_internal_marginal_times(const pba_engine* e, double* ms5) {
   for (int k = 0; k < pba_engine::kMargKernels; ++k) ms5[k] = e->marg_ms[k];
+}
+
+// ---- outlier culling (pba_cull.h) -------------------------------------------------------------------------------------------------
+int pba_get_block_costs(pba_engine* e, double* cost) {
+  if (!e || !cost) return PBA_ERR_INVALID;
+  { const int rc0 = check_ready(e, "pba_get_block_costs"); if (rc0) return rc0; }
+  PBA_ENTER(e);
+  { const int rc = pba_linearize(e, nullptr); if (rc) return rc; }
+  HIP_TRY(e, hipMemcpyAsync(cost, e->d_rec[e->cur] + 5 * e->rec_stride, sizeof(double) * e->n_obs, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  return PBA_OK;
+}
+
+// Test hook: the select kernels of pba_cull on a caller's array; *out = the k-th smallest of v [n] (0-based) in the order of the bit patterns
+int pba_internal_select_u64order(pba_engine* e, const double* v, int64_t n, int64_t k, double* out) {
+  if (!e || !v || !out || n < 1 || n > INT32_MAX || k < 0 || k >= n) return PBA_ERR_INVALID;
+  PBA_ENTER(e);
+  int rc;
+  if ((rc = dev_alloc(e, &e->d_cull_hist, (size_t)kCullPasses * kCullBins))) return rc;
+  if ((rc = dev_alloc(e, &e->d_cull_sel, (size_t)kCullSelWords))) return rc;
+  DeviceTemp<uint64_t> dv;
+  HIP_TRY(e, dv.alloc((size_t)n));
+  HIP_TRY(e, hipMemcpyAsync(dv.p, v, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, e->stream));
+  cull_enqueue_select(e->stream, dv.p, n, (uint32_t)k, e->d_cull_hist, e->d_cull_sel, 0, 0.0, 0.0);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipMemcpyAsync(out, e->d_cull_sel, sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  return PBA_OK;
+}
+
+// Every refusal that can be known in advance comes before the first launch; the verdict is computed into cull-owned buffers, the host
+// reads the keep bytes, the point map and the counts, and only then is anything of the engine's problem replaced.
+int pba_cull(pba_engine* e, const pba_cull_options* o, uint8_t* block_keep, int32_t* point_map, pba_cull_info* info) {
+  if (!e || !o) return PBA_ERR_INVALID;
+  pba_cull_info inf{};
+  if (info) *info = inf;
+  if (!(o->min_cost >= 0.0) || !std::isfinite(o->min_cost)) return fail(e, PBA_ERR_INVALID, "pba_cull: min_cost = %g must be finite and >= 0", o->min_cost);
+  if (!(o->factor >= 0.0) || !std::isfinite(o->factor)) return fail(e, PBA_ERR_INVALID, "pba_cull: factor = %g must be finite and >= 0", o->factor);
+  if (!(o->quantile >= 0.0 && o->quantile <= 1.0)) return fail(e, PBA_ERR_INVALID, "pba_cull: quantile = %g must be in [0, 1]", o->quantile);
+  if (o->min_observations < 1) return fail(e, PBA_ERR_INVALID, "pba_cull: min_observations = %d must be >= 1", o->min_observations);
+  if (const char* why = mode_conflict(modes_present(e, e->comm.multi()), kModeCull)) return fail(e, PBA_ERR_INVALID, "pba_cull: %s", why);
+  { const int rc0 = check_ready(e, "pba_cull"); if (rc0) return rc0; }
+  PBA_ENTER(e);
+  int rc;
+  if ((rc = pba_linearize(e, nullptr))) return rc;
+  const int n_obs = e->n_obs, n_points = e->n_points, cur = e->cur;
+  const int pt_blocks = (n_points + kCullThreads - 1) / kCullThreads, obs_blocks = (n_obs + kCullThreads - 1) / kCullThreads;
+  if ((rc = dev_alloc(e, &e->d_cull_hist, (size_t)kCullPasses * kCullBins))) return rc;
+  if ((rc = dev_alloc(e, &e->d_cull_sel, (size_t)kCullSelWords))) return rc;
+  if ((rc = dev_alloc(e, &e->d_cull_pt_cnt, (size_t)n_points))) return rc;
+  if ((rc = dev_alloc(e, &e->d_cull_part, (size_t)pt_blocks))) return rc;
+  if ((rc = dev_alloc(e, &e->d_cull_off, (size_t)pt_blocks))) return rc;
+  if ((rc = dev_alloc(e, &e->d_cull_tot, (size_t)kCullTotals))) return rc;
+  if ((rc = dev_alloc(e, &e->d_cull_map, (size_t)n_points))) return rc;
+  if ((rc = dev_alloc(e, &e->d_cull_dst, (size_t)n_obs))) return rc;
+  if ((rc = dev_alloc(e, &e->d_cull_keep, (size_t)n_obs))) return rc;
+
+  const int64_t k = (int64_t)std::floor(o->quantile * (double)(n_obs - 1));
+  const double* cost = e->d_rec[cur] + 5 * e->rec_stride;
+  cull_enqueue_select(e->stream, reinterpret_cast<const uint64_t*>(cost), n_obs, (uint32_t)k, e->d_cull_hist, e->d_cull_sel, 1, o->min_cost, o->factor);
+  CullParams cp{};
+  cp.cost = cost; cp.sel = e->d_cull_sel; cp.pt_begin = e->d_pt_begin; cp.obs_point = e->d_obs_point; cp.obs_slot = e->d_obs_slot;
+  cp.pt_cnt = e->d_cull_pt_cnt; cp.part = e->d_cull_part; cp.off = e->d_cull_off; cp.tot = e->d_cull_tot; cp.point_map = e->d_cull_map;
+  cp.obs_dst = e->d_cull_dst; cp.keep = e->d_cull_keep;
+  cp.n_points = n_points; cp.n_obs = n_obs; cp.n_part = pt_blocks; cp.min_observations = o->min_observations;
+  hipLaunchKernelGGL(k_cull_verdict, dim3(pt_blocks), dim3(kCullThreads), 0, e->stream, cp);
+  hipLaunchKernelGGL(k_cull_offsets, dim3(1), dim3(kCullThreads), 0, e->stream, cp);
+  hipLaunchKernelGGL(k_cull_index, dim3(pt_blocks), dim3(kCullThreads), 0, e->stream, cp);
+  HIP_TRY(e, hipGetLastError());
+  uint64_t sel[kCullSelWords] = {0, 0, 0};
+  int32_t tot[kCullTotals] = {0, 0, 0, 0};
+  std::vector<uint8_t> keep(n_obs);
+  std::vector<int32_t> map(n_points);
+  HIP_TRY(e, hipMemcpyAsync(sel, e->d_cull_sel, sizeof(sel), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(tot, e->d_cull_tot, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(keep.data(), e->d_cull_keep, (size_t)n_obs, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(map.data(), e->d_cull_map, sizeof(int32_t) * n_points, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+
+  inf.n_blocks_before = inf.n_blocks_after = n_obs;
+  inf.n_points_before = inf.n_points_after = n_points;
+  std::memcpy(&inf.quantile_cost, &sel[0], sizeof(double));
+  std::memcpy(&inf.threshold, &sel[1], sizeof(double));
+  if (sel[2]) {
+    if (info) *info = inf;
+    return fail(e, PBA_ERR_NUMERIC, "pba_cull: factor * quantile_cost = %g * %g is not finite", o->factor, inf.quantile_cost);
+  }
+  inf.n_points_after = tot[0]; inf.n_blocks_after = tot[1]; inf.n_blocks_over_threshold = tot[2]; inf.n_blocks_by_point_rule = tot[3];
+  if (block_keep) std::memcpy(block_keep, keep.data(), keep.size());
+  if (point_map) std::memcpy(point_map, map.data(), sizeof(int32_t) * map.size());
+  if (info) *info = inf;
+  if (!o->apply || inf.n_blocks_after == n_obs) return PBA_OK;
+  if (inf.n_points_after == 0)
+    return fail(e, PBA_ERR_INVALID, "pba_cull: no point would be left (threshold %g, quantile cost %g, min_observations %d)", inf.threshold,
+                inf.quantile_cost, o->min_observations);
+
+  // the survivors, gathered into fresh buffers that then take the place of the engine's
+  const int PD = pba_internal_patch_len(e);
+  if ((rc = dev_alloc(e, &e->d_cull_xyz, (size_t)3 * n_points))) return rc;
+  if ((rc = dev_alloc(e, &e->d_cull_desc, (size_t)n_points * PD))) return rc;
+  if ((rc = dev_alloc(e, &e->d_cull_obs_point, (size_t)n_obs))) return rc;
+  if ((rc = dev_alloc(e, &e->d_cull_obs_slot, (size_t)n_obs))) return rc;
+  if (e->inverse_depth && (rc = dev_alloc(e, &e->d_cull_rays, (size_t)6 * n_points))) return rc;
+  cp.obs_point_new = e->d_cull_obs_point; cp.obs_slot_new = e->d_cull_obs_slot;
+  const auto row_grid = [&](int row_len) { return dim3((unsigned)std::min<int64_t>(((int64_t)n_points * row_len + kCullThreads - 1) / kCullThreads, 1 << 16)); };
+  hipLaunchKernelGGL(k_cull_gather_obs, dim3(obs_blocks), dim3(kCullThreads), 0, e->stream, cp);
+  hipLaunchKernelGGL(k_cull_gather_rows<double>, row_grid(3), dim3(kCullThreads), 0, e->stream, (const double*)e->d_xyz[cur], e->d_cull_xyz,
+                     (const int32_t*)e->d_cull_map, n_points, 3);
+  hipLaunchKernelGGL(k_cull_gather_rows<float>, row_grid(PD), dim3(kCullThreads), 0, e->stream, (const float*)e->d_desc, e->d_cull_desc,
+                     (const int32_t*)e->d_cull_map, n_points, PD);
+  if (e->inverse_depth)
+    hipLaunchKernelGGL(k_cull_gather_rows<double>, row_grid(6), dim3(kCullThreads), 0, e->stream, (const double*)e->d_rays, e->d_cull_rays,
+                       (const int32_t*)e->d_cull_map, n_points, 6);
+  HIP_TRY(e, hipGetLastError());
+  // the surviving lists on the host, for the tile builder pba_set_problem runs
+  std::vector<int32_t> op((size_t)inf.n_blocks_after), os((size_t)inf.n_blocks_after);
+  {
+    size_t d = 0;
+    for (int p = 0; p < n_points; ++p)
+      for (int ob = e->h_pt_begin[p]; ob < e->h_pt_begin[p + 1]; ++ob)
+        if (keep[ob]) { op[d] = map[p]; os[d] = e->h_obs_slot[ob]; ++d; }
+  }
+  if (e->inverse_depth) {
+    for (int p = 0; p < n_points; ++p)
+      if (map[p] >= 0 && map[p] != p) std::memmove(&e->h_rays[6 * (size_t)map[p]], &e->h_rays[6 * (size_t)p], 6 * sizeof(double));
+    e->h_rays.resize((size_t)6 * inf.n_points_after);
+  }
+  ProblemLayout L;
+  if ((rc = problem_layout(e, inf.n_points_after, inf.n_blocks_after, op.data(), os.data(), &L))) return rc;
+  e->mem.exchange(&e->d_xyz[cur], &e->d_cull_xyz);
+  e->mem.exchange(&e->d_desc, &e->d_cull_desc);
+  e->mem.exchange(&e->d_obs_point, &e->d_cull_obs_point);
+  e->mem.exchange(&e->d_obs_slot, &e->d_cull_obs_slot);
+  if (e->inverse_depth) e->mem.exchange(&e->d_rays, &e->d_cull_rays);
+  if ((rc = problem_reserve(e, L, PD))) return rc;
+  if ((rc = problem_upload_tables(e, L))) return rc;
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  problem_installed(e, &L);
+  invalidate(e, kInProblem);
+  inf.applied = 1;
+  if (info) *info = inf;
+  return PBA_OK;
 }
 
 int pba_get_obs_records(pba_engine* e, double* rec6) {

@@ -19,6 +19,8 @@ int pba_internal_points_constant(const pba_engine* e);
 int64_t pba_internal_program_blocks(const pba_engine* e);
 void pba_internal_covariance_times(const pba_engine* e, double* ms4);      // event time of the kernels of the last pba_covariance
 void pba_internal_marginal_times(const pba_engine* e, double* ms5);        // event time of the kernels of the last pba_marginalize
+// test hook: the radix-select kernels of pba_cull on a caller's array; *out = the k-th smallest of v [n] (0-based) by 64-bit pattern
+int pba_internal_select_u64order(pba_engine* e, const double* v, int64_t n, int64_t k, double* out);
 double pba_internal_fixed_cost(const pba_engine* e);
 int pba_internal_refuse(pba_engine* e, int code, const char* msg);
 int pba_internal_allreduce_host(pba_engine* e, double* v, int n, int op);

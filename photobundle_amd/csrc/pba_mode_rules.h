@@ -1,7 +1,7 @@
 // pba_mode_rules.h -- THE table of features that do not combine, with the sentence each refusal says.  A row names two features and
 // holds one sentence per call order: `then_b` is said when `a` is present and `b` is switched on, `then_a` the other way round.  A row
 // without a second sentence has a `b` that is never present when something is switched on (the sampler flags are fixed at pba_create;
-// the covariance output and a batch are calls, not states): asked the other way round it answers with the same sentence.  The caller
+// the covariance output, a batch and a cull are calls, not states): asked the other way round it answers with the same sentence.  The caller
 // adds its prefix ("pba_set_cameras_constant: ") and suffix ("(%d free cameras)") and decides what counts as present (multi-rank:
 // comm.multi() in the setters, world > 1 at pba_comm_init_*).  With several conflicts present the first row wins: the order of the
 // rows is part of the interface.  No HIP header is needed: plain C++ compiles it (tests/mode_rules_probe.cpp does).
@@ -12,7 +12,7 @@ namespace pba {
 enum ModeFeature : unsigned {      // one bit each
   kModeMulti = 1, kModeInverseDepth = 2, kModeSweep = 4 /* pba_config.flags bits 1-2 */, kModeWide = 8, kModePointsConst = 16, kModeCamsConst = 32,
   kModeAnchors = 64 /* two or more constant slots */, kModeCovariance = 128 /* pba_covariance */, kModeBatch = 256 /* pba_solve_batch */,
-  kModePrior = 512 /* pba_set_camera_prior; pba_marginalize asks as if it switched one on */
+  kModePrior = 512 /* pba_set_camera_prior; pba_marginalize asks as if it switched one on */, kModeCull = 1024 /* pba_cull */
 };
 struct ModeRule { unsigned a, b; const char* then_b; const char* then_a; };
 constexpr ModeRule kModeRules[] = {
@@ -48,6 +48,8 @@ constexpr ModeRule kModeRules[] = {
      "the camera prior (pba_set_camera_prior) is not built for the inverse-depth mode"},
     {kModePrior, kModeCovariance, "the camera prior (pba_set_camera_prior) is set: a covariance that ignored it would be wrong", nullptr},
     {kModePrior, kModeBatch, "the camera prior (pba_set_camera_prior) solves alone", nullptr},
+    {kModeMulti, kModeCull, "multi-rank engines (pba_comm_*) are not built for culling: the order statistic would need an exchange", nullptr},
+    {kModeSweep, kModeCull, "the precision-sweep sampler modes (pba_config.flags bits 1-2) are not built for culling", nullptr},
 };
 
 // Why feature `on` (one bit) cannot be switched on next to the features `present` (nullptr: it can); *with: the feature in its way

@@ -363,6 +363,39 @@ class Engine:
         out.update(slots=slots[:k].copy(), x0=x0[:k].copy(), Lambda=Lm[:36 * k * k].reshape(6 * k, 6 * k).copy(), eta=eta[:6 * k].copy(), c=c.value)
         return out
 
+    # ---- outlier culling ---------------------------------------------------------------------------------------
+    def block_costs(self):
+        """pba_get_block_costs: the loss-corrected cost of every residual block at the current state, [n_obs]."""
+        c = np.zeros(self.n_obs)
+        self._check(self._L.pba_get_block_costs(self._h, _ptr(c)), "pba_get_block_costs")
+        return c
+
+    def cull(self, min_cost=0.0, factor=0.0, quantile=0.5, min_observations=2, apply=True):
+        """pba_cull: the verdict over the block costs and, with apply, the engine's problem replaced by the survivors (include/pba.h).
+        Returns (block_keep [n_obs before] uint8, point_map [n_points before] int32 with -1 for a point that leaves, info dict);
+        n_points / n_obs follow an applied cull.  Raises EngineError otherwise; its `status` and `info` attributes carry the status
+        code and the info fields, `block_keep` and `point_map` the tables (filled by the "no point would be left" refusal)."""
+        o = _lib.CullOptions(float(min_cost), float(factor), float(quantile), int(min_observations), 1 if apply else 0)
+        info = _lib.CullInfo()
+        keep = np.zeros(self.n_obs, np.uint8)
+        pmap = np.zeros(self.n_points, np.int32)
+        rc = self._L.pba_cull(self._h, C.byref(o), _ptr(keep), _ptr(pmap), C.byref(info))
+        fields = {f: getattr(info, f) for f, _ in _lib.CullInfo._fields_}
+        if rc != 0:
+            err = EngineError("pba_cull: %s (%s)" % (self._L.pba_status_string(rc).decode(), self._L.pba_last_error(self._h).decode()))
+            err.status, err.info, err.block_keep, err.point_map = rc, fields, keep, pmap
+            raise err
+        if info.applied:
+            self.n_points, self.n_obs = info.n_points_after, info.n_blocks_after
+        return keep, pmap, fields
+
+    def select_u64order(self, v, k):
+        """Test hook (pba_internal_select_u64order): the k-th smallest of v by 64-bit pattern, through the select kernels of pba_cull."""
+        v = np.ascontiguousarray(v, np.float64).ravel()
+        out = C.c_double(0.0)
+        self._check(self._L.pba_internal_select_u64order(self._h, _ptr(v), v.shape[0], int(k), C.byref(out)), "pba_internal_select_u64order")
+        return out.value
+
     # ---- multi-GPU -------------------------------------------------------------------------------------------
     @staticmethod
     def comm_unique_id():

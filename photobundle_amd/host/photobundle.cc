@@ -173,7 +173,12 @@ PhotometricBundleAdjustment::Options::Options(const utils::ConfigFile& cf)
       camerasConstant((bool)cf.get<int>("camerasConstant", 0)),
       numConstantFrames(cf.get<int>("numConstantFrames", 1)),
       computeCovariance((bool)cf.get<int>("computeCovariance", 0)),
-      marginalize((bool)cf.get<int>("marginalize", 0)) {}
+      marginalize((bool)cf.get<int>("marginalize", 0)),
+      outlierPasses(cf.get<int>("outlierPasses", 0)),
+      outlierQuantile(cf.get<double>("outlierQuantile", 0.5)),
+      outlierFactor(cf.get<double>("outlierFactor", 3.0)),
+      outlierMinCost(cf.get<double>("outlierMinCost", 0.0)),
+      outlierMinObservations(cf.get<int>("outlierMinObservations", 2)) {}
 
 std::ostream& operator<<(std::ostream& os, const PhotometricBundleAdjustment::Options& o) {
   using DT = PhotometricBundleAdjustment::Options::DescriptorType;
@@ -184,7 +189,9 @@ std::ostream& operator<<(std::ostream& os, const PhotometricBundleAdjustment::Op
      << "\ndoGaussianWeighting = " << (o.doGaussianWeighting ? 1 : 0) << "\nrobustThreshold = " << o.robustThreshold
      << "\ndescriptorType = " << dt << "\nnumThreads = " << o.numThreads << "\nverbose = " << (o.verbose ? 1 : 0) << "\ndevice = " << o.device
      << "\ncamerasConstant = " << (o.camerasConstant ? 1 : 0) << "\nnumConstantFrames = " << o.numConstantFrames
-     << "\ncomputeCovariance = " << (o.computeCovariance ? 1 : 0) << "\nmarginalize = " << (o.marginalize ? 1 : 0) << "\n";
+     << "\ncomputeCovariance = " << (o.computeCovariance ? 1 : 0) << "\nmarginalize = " << (o.marginalize ? 1 : 0)
+     << "\noutlierPasses = " << o.outlierPasses << "\noutlierQuantile = " << o.outlierQuantile << "\noutlierFactor = " << o.outlierFactor
+     << "\noutlierMinCost = " << o.outlierMinCost << "\noutlierMinObservations = " << o.outlierMinObservations << "\n";
   return os;
 }
 
@@ -254,6 +261,7 @@ struct PhotometricBundleAdjustment::ScenePoint {
   std::vector<double> descriptor;
   double saliency = 0.0;
   bool was_refined = false;
+  bool ref_culled = false;       // Options::outlierPasses: the block of the reference frame was culled (the frame stays in `f`)
   int x0 = 0, y0 = 0;
   ScenePoint(const Vec3& X_, uint32_t f_id) : X(X_), X_original(X_) { f.reserve(8); f.push_back(f_id); }
   uint32_t refFrameId() const { return f.front(); }
@@ -278,6 +286,18 @@ PhotometricBundleAdjustment::PhotometricBundleAdjustment(const Calibration& cali
   if (options.marginalize && options.computeCovariance)
     throw std::invalid_argument("marginalize with computeCovariance: a covariance that ignored the prior would be wrong, and the engine "
                                 "refuses it (pba_covariance)");
+  if (options.outlierPasses < 0)
+    throw std::invalid_argument("outlierPasses = " + std::to_string(options.outlierPasses) + " is negative: 0 switches the outlier culling off");
+  if (options.outlierPasses > 0) {
+    if (!(options.outlierQuantile >= 0.0 && options.outlierQuantile <= 1.0))
+      throw std::invalid_argument("outlierQuantile = " + std::to_string(options.outlierQuantile) + " is outside 0 .. 1");
+    if (!(options.outlierFactor >= 0.0) || !std::isfinite(options.outlierFactor))
+      throw std::invalid_argument("outlierFactor = " + std::to_string(options.outlierFactor) + " must be finite and >= 0 (0: outlierMinCost alone is the threshold)");
+    if (!(options.outlierMinCost >= 0.0) || !std::isfinite(options.outlierMinCost))
+      throw std::invalid_argument("outlierMinCost = " + std::to_string(options.outlierMinCost) + " must be finite and >= 0");
+    if (options.outlierMinObservations < 1)
+      throw std::invalid_argument("outlierMinObservations = " + std::to_string(options.outlierMinObservations) + " is below 1: a point needs at least one residual block");
+  }
   // Multi-channel descriptor types: the reference's debug builds stop at `assert(p0.size() == w.size())`
   // (photobundle.cc:684: C P descriptor entries against P patch weights); its release builds run, with the weights
   // restarting per channel (:714-721), and that is what is built here.
@@ -357,6 +377,27 @@ Mat44 PhotometricBundleAdjustment::trackFrame(const uint8_t* image, const Mat44&
   so.verbose = 0;
   pba_solver_summary summary;
   check(e, pba_solve(e, &so, &summary, nullptr, 0), "pba_solve (trackFrame)");
+  // TrackOptions::outlierPasses: cull pose-only (one block per point: a point stays with its one block), then align again
+  if (topt.outlierPasses > 0 && summary.termination_type != 2) {
+    const double first_initial_cost = summary.initial_cost;
+    pba_cull_options co;
+    co.min_cost = op.outlierMinCost; co.factor = op.outlierFactor; co.quantile = op.outlierQuantile; co.min_observations = 1; co.apply = 1;
+    for (int pass = 0; pass < topt.outlierPasses; ++pass) {
+      pba_cull_info info;
+      const int rc = pba_cull(e, &co, nullptr, nullptr, &info);
+      if (rc == PBA_ERR_INVALID || rc == PBA_ERR_NUMERIC) {
+        std::fprintf(stderr, "trackFrame: outlier pass %d stopped: pba_cull: %s (%s)\n", pass, pba_status_string(rc), pba_last_error(e));
+        break;
+      }
+      check(e, rc, "pba_cull (trackFrame)");
+      if (!info.applied) break;
+      tr.numCulledBlocks += info.n_blocks_before - info.n_blocks_after;
+      tr.numCulledPoints += info.n_points_before - info.n_points_after;
+      check(e, pba_solve(e, &so, &summary, nullptr, 0), "pba_solve (trackFrame, outlier pass)");
+      if (summary.termination_type == 2) break;
+    }
+    summary.initial_cost = first_initial_cost;
+  }
   check(e, pba_get_state(e, cams, nullptr), "pba_get_state");
   tr.initialCost = summary.initial_cost; tr.finalCost = summary.final_cost;
   tr.numIterations = summary.num_successful_steps + summary.num_unsuccessful_steps - 1;
@@ -651,6 +692,8 @@ struct PhotometricBundleAdjustment::OptimizeState {
   int n_anchored = 0;      // oldest frames held constant through pba_set_cameras_anchored (0: the one-slot call, as ever)
   std::vector<double> cams, xyz;
   std::vector<ScenePoint*> selected;
+  std::vector<int32_t> obs_point, obs_slot;      // the observation list the engine holds (Options::outlierPasses maps removed blocks back)
+  int culled_blocks = 0, culled_points = 0;      // Options::outlierPasses, summed over the passes
   pba_solver_options so;
   pba_solver_summary summary;
   std::vector<pba_iteration_summary> its;
@@ -668,9 +711,63 @@ void PhotometricBundleAdjustment::optimize(Result* result) {
   OptimizeState st;
   if (optimizeAssemble(st)) {
     check(_engine, pba_solve(_engine, &st.so, &st.summary, st.its.data(), (int32_t)st.its.size()), "pba_solve");
+    if (_options_ptr->outlierPasses > 0) cullAndResolve(st);
     st.lap(3);
   }
   optimizeFinish(st, result);
+}
+
+// Options::outlierPasses: pba_cull, then pba_solve on the survivors, until the passes are used up or a cull removes nothing.  The state
+// follows the engine's problem: `selected` and the observation list shrink through the cull's tables, and every removed block leaves
+// its scene point's visibility list.  A cull the engine refuses (no point would be left, a non-finite threshold) ends the passes and
+// says so on stderr; the solve that stands is the last one.
+void PhotometricBundleAdjustment::cullAndResolve(OptimizeState& st) {
+  const Options& op = *_options_ptr;
+  const uint32_t window = (uint32_t)op.slidingWindowSize;
+  const double first_initial_cost = st.summary.initial_cost;
+  pba_cull_options co;
+  co.min_cost = op.outlierMinCost; co.factor = op.outlierFactor; co.quantile = op.outlierQuantile;
+  co.min_observations = op.outlierMinObservations; co.apply = 1;
+  for (int pass = 0; pass < op.outlierPasses; ++pass) {
+    std::vector<uint8_t> keep(st.obs_point.size());
+    std::vector<int32_t> map(st.selected.size());
+    pba_cull_info info;
+    const int rc = pba_cull(_engine, &co, keep.data(), map.data(), &info);
+    if (rc == PBA_ERR_INVALID || rc == PBA_ERR_NUMERIC) {
+      std::fprintf(stderr, "outlier pass %d stopped: pba_cull: %s (%s)\n", pass, pba_status_string(rc), pba_last_error(_engine));
+      break;
+    }
+    check(_engine, rc, "pba_cull");
+    if (op.verbose)
+      std::fprintf(stderr, "outlier pass %d: %d -> %d residual blocks (%d over the threshold %.6g, %d by the point rule), %d -> %d points\n", pass,
+                   info.n_blocks_before, info.n_blocks_after, info.n_blocks_over_threshold, info.threshold, info.n_blocks_by_point_rule,
+                   info.n_points_before, info.n_points_after);
+    if (!info.applied) break;
+    // removed blocks: their frame leaves the point's visibility list (the reference frame is marked instead, ScenePoint::ref_culled)
+    size_t n_keep = 0;
+    for (size_t o = 0; o < keep.size(); ++o) {
+      const int32_t p = st.obs_point[o], slot = st.obs_slot[o];
+      if (keep[o]) {
+        st.obs_point[n_keep] = map[(size_t)p];
+        st.obs_slot[n_keep++] = slot;
+        continue;
+      }
+      ScenePoint* pt = st.selected[(size_t)p];
+      const uint32_t id = st.frame_id_start + ((uint32_t)slot + window - st.frame_id_start % window) % window;
+      if (id == pt->refFrameId()) pt->ref_culled = true;
+      else pt->f.erase(std::remove(pt->f.begin(), pt->f.end(), id), pt->f.end());
+    }
+    st.obs_point.resize(n_keep);
+    st.obs_slot.resize(n_keep);
+    for (size_t p = 0; p < map.size(); ++p)
+      if (map[p] >= 0) st.selected[(size_t)map[p]] = st.selected[p];
+    st.selected.resize((size_t)info.n_points_after);
+    st.xyz.resize(3 * st.selected.size());
+    st.culled_blocks += info.n_blocks_before - info.n_blocks_after;
+    st.culled_points += info.n_points_before - info.n_points_after;
+    check(_engine, pba_solve(_engine, &st.so, &st.summary, st.its.data(), (int32_t)st.its.size()), "pba_solve (outlier pass)");
+  }
+  st.summary.initial_cost = first_initial_cost;
 }
 
 bool PhotometricBundleAdjustment::optimizeAssemble(OptimizeState& st) {
@@ -691,7 +788,8 @@ bool PhotometricBundleAdjustment::optimizeAssemble(OptimizeState& st) {
   std::vector<ScenePoint*>& selected = st.selected;
   std::vector<double>& xyz = st.xyz;
   std::vector<double> desc;
-  std::vector<int32_t> obs_point, obs_slot;
+  std::vector<int32_t>& obs_point = st.obs_point;
+  std::vector<int32_t>& obs_slot = st.obs_slot;
   selected.reserve(_scene_points.size());
   xyz.reserve(3 * _scene_points.size());
   desc.reserve((size_t)P * _scene_points.size());
@@ -702,7 +800,8 @@ bool PhotometricBundleAdjustment::optimizeAssemble(OptimizeState& st) {
       int32_t slots[PBA_MAX_FRAMES];
       int n_slots = 0;
       for (uint32_t id : pt->f)
-        if (id >= frame_id_start && id <= frame_id_end && n_slots < PBA_MAX_FRAMES) slots[n_slots++] = (int32_t)(id % window);
+        if (id >= frame_id_start && id <= frame_id_end && n_slots < PBA_MAX_FRAMES && !(pt->ref_culled && id == pt->refFrameId()))
+          slots[n_slots++] = (int32_t)(id % window);
       if (n_slots == 0) continue;
       std::sort(slots, slots + n_slots);
       pt->was_refined = true;
@@ -886,6 +985,8 @@ void PhotometricBundleAdjustment::optimizeFinish(OptimizeState& st, Result* resu
     result->numSuccessfulStep = summary.num_successful_steps;
     result->totalTime = summary.total_time_in_seconds;
     result->numResiduals = summary.num_residuals;
+    result->numCulledBlocks = st.culled_blocks;
+    result->numCulledPoints = st.culled_points;
     result->message = summary.message;
     result->iterationSummary.clear();
     for (int i = 0; i < summary.num_iterations; ++i) {
@@ -955,6 +1056,10 @@ void PhotometricBundleAdjustment::addFrames(const std::vector<PhotometricBundleA
   for (size_t i = 0; i < n; ++i)
     if (instances[i]->_options_ptr->marginalize)
       throw std::invalid_argument("addFrames: Options::marginalize solves alone (pba_solve_batch refuses an engine that holds a prior); use addFrame");
+  for (size_t i = 0; i < n; ++i)
+    if (instances[i]->_options_ptr->outlierPasses > 0)
+      throw std::invalid_argument("addFrames: Options::outlierPasses solves alone (a cull sits between two solves of one window, and batched culling is "
+                                  "not built); use addFrame");
   auto result_of = [&](size_t i) { return results.empty() ? nullptr : results[i]; };
   std::vector<size_t> due;
   for (size_t i = 0; i < n; ++i)

@@ -57,6 +57,10 @@ struct TrackOptions {
   int maxIterations = 50;
   int minPoints = 64;                 // below it the frame is not tracked
   bool computeCovariance = false;     // pba_covariance after the alignment: the 6x6 covariance of the tracked pose
+  // outlier culling (new): after the alignment up to outlierPasses rounds of pba_cull + pba_solve, pose-only (every point has one block
+  // here, so a point stays with one surviving block: min_observations = 1); threshold from Options::outlierQuantile / outlierFactor /
+  // outlierMinCost of the instance.  Stops early when a cull removes nothing (or would remove everything).  0: as without the field.
+  int outlierPasses = 0;
 };
 struct TrackResult {
   bool tracked = false;
@@ -64,6 +68,8 @@ struct TrackResult {
   double initialCost = -1.0, finalCost = -1.0;
   int numIterations = 0;
   std::string message;
+  int numCulledBlocks = 0, numCulledPoints = 0;   // TrackOptions::outlierPasses: summed over the passes (costs, iterations and message: the last solve's;
+                                                  // initialCost: the first solve's)
   // TrackOptions::computeCovariance: (J^T J)^-1 of the tracked camera, row-major 6x6, unit residual variance, in the engine's camera
   // parameters (angle-axis and translation of the WORLD->CAMERA transform, not the frame-to-frame pose trackFrame returns); minPivot is
   // the smallest Cholesky pivot of its unit-diagonal form, in (0, 1].  covarianceOk = false: not asked for, not tracked, or the call
@@ -147,6 +153,21 @@ class PhotometricBundleAdjustment {
     // marginalisation that fails (a singular block) clears the prior, says so on stderr and does not stop the run.  Off: the class
     // produces what it produced without the field.
     bool marginalize = false;
+    // outlier culling (new; the step the reference leaves as a TODO after its solve): after pba_solve, optimize() runs pba_cull then
+    // pba_solve again, up to outlierPasses times, and stops early when a cull removes nothing.  A residual block goes when its
+    // loss-corrected cost exceeds max(outlierMinCost, outlierFactor x the outlierQuantile-quantile of all block costs); a point that keeps
+    // fewer than outlierMinObservations blocks goes with all of them (include/pba.h, pba_cull).  The frame of every removed block leaves
+    // the scene point's visibility list, so later windows do not add it again; the point's REFERENCE frame stays in the list (it decides
+    // when the point is evicted) and is only marked, which keeps its block out as well.  Covariance and marginalisation see the culled
+    // problem.  The last four are read only when outlierPasses > 0; their defaults are untuned on real imagery.  Ranges (else
+    // std::invalid_argument from the constructor): outlierPasses >= 0, outlierQuantile in [0, 1], outlierFactor >= 0 and finite,
+    // outlierMinCost >= 0 and finite, outlierMinObservations >= 1.  addFrames throws with outlierPasses > 0 (batched culling is not
+    // built).  0: the class produces what it produced without the fields, and no new call reaches the engine.
+    int outlierPasses = 0;
+    double outlierQuantile = 0.5;
+    double outlierFactor = 3.0;
+    double outlierMinCost = 0.0;
+    int outlierMinObservations = 2;
 
     Options() {}
     Options(const utils::ConfigFile& cf);
@@ -169,6 +190,9 @@ class PhotometricBundleAdjustment {
                                                     // (part of finalCost); 0 without a prior
     int numSuccessfulStep = 0;
     int numResiduals = 0;
+    // Options::outlierPasses: residual blocks and points the culls of this optimisation removed, summed over the passes.  initialCost is
+    // then the FIRST solve's; finalCost, numSuccessfulStep, numResiduals, totalTime, message and iterationSummary are the LAST solve's
+    int numCulledBlocks = 0, numCulledPoints = 0;
     double totalTime = -1.0;                        // seconds
     std::string message;
     std::vector<ceres::IterationSummary> iterationSummary;
@@ -211,6 +235,7 @@ class PhotometricBundleAdjustment {
   bool addFrameImpl(const uint8_t* image, const float* depth_map, const Mat44& T, Result* result, bool defer);
   bool optimizeAssemble(OptimizeState& st);
   void optimizeFinish(OptimizeState& st, Result* result);
+  void cullAndResolve(OptimizeState& st);      // Options::outlierPasses, between the solve and optimizeFinish
   typedef UniquePointer<ScenePoint> ScenePointPointer;
   typedef std::vector<ScenePointPointer> ScenePointPointerList;
 
