@@ -30,6 +30,31 @@
 
 using namespace pba;
 
+// Event times of the N kernels of one off-loop call (pba_covariance, pba_marginalize) under event profiling (pba_set_profiling(e, 1)):
+// one begin / end pair of events per kernel, created on first use; ms[k] of the last call, -1: kernel k did not run or profiling was off
+template <int N>
+struct KernelTimes {
+  hipEvent_t ev[2 * N] = {};
+  double ms[N] = {};
+  bool on = false, ran[N] = {};
+  int start(pba::Handle* h, bool timed) {
+    on = timed;
+    for (bool& r : ran) r = false;
+    if (timed && !ev[0])
+      for (hipEvent_t& x : ev) { const int rc = handle_event(h, &x); if (rc) return rc; }
+    return PBA_OK;
+  }
+  void begin(const pba::Handle* h, int k) { if (on) { (void)hipEventRecord(ev[2 * k], h->stream); ran[k] = true; } }
+  void end(const pba::Handle* h, int k) { if (on) (void)hipEventRecord(ev[2 * k + 1], h->stream); }
+  void collect() {
+    for (int k = 0; k < N; ++k) {
+      float t = 0.0f;
+      ms[k] = (on && ran[k] && hipEventElapsedTime(&t, ev[2 * k], ev[2 * k + 1]) == hipSuccess) ? (double)t : -1.0;
+    }
+  }
+  void copy_to(double* out) const { for (int k = 0; k < N; ++k) out[k] = ms[k]; }
+};
+
 struct pba_engine : pba::Handle {      // (device, stream, err, mem, events)
   pba_config cfg{};
 
@@ -178,17 +203,17 @@ struct pba_engine : pba::Handle {      // (device, stream, err, mem, events)
   double* d_pts_V = nullptr;        // [n_points][9] test hook (pba_config.flags bit 0)
   double* d_pts_rhs = nullptr;      // [n_points][3]
 
-  // covariance output (pba_covariance, pba_cov.h): everything on first use, nothing shared with the LM
+  // the point elimination of pba_covariance and pba_marginalize (pba_elim.h): everything on first use, nothing shared with the LM; a
+  // call writes every buffer it reads, so the two calls use one set
+  double* d_elim_X = nullptr;       // [n_points][6] triangular factor of V^-1 (marginalisation: zero outside the marginalised points)
+  double* d_elim_part = nullptr;    // [point blocks][kCovPart or kMargPart]
+  double* d_elim_S = nullptr;       // [n][n] undamped, unscaled reduced camera matrix (marginalisation: of the marginalised points)
+  double* d_elim_info = nullptr;    // [3] (k_cov_invert: 2, k_marg_eliminate: 3)
+  // covariance output (pba_covariance, pba_cov.h)
   double* d_cov_P = nullptr;        // [n_points][6] V^-1
-  double* d_cov_X = nullptr;        // [n_points][6] its triangular factor
-  double* d_cov_part = nullptr;     // [point blocks][kCovPart]
-  double* d_cov_S = nullptr;        // [n][n] undamped, unscaled reduced camera matrix
-  double* d_cov_C = nullptr;        // [n][n] its inverse
+  double* d_cov_C = nullptr;        // [n][n] the inverse of S
   double* d_cov_pp = nullptr;       // [n_points][9]
-  double* d_cov_info = nullptr;     // [2] (k_cov_invert)
-  static constexpr int kCovKernels = 4;    // k_cov_point, k_cov_schur, k_cov_invert, k_cov_points
-  hipEvent_t cov_ev[2 * kCovKernels] = {}; // event profiling (pba_set_profiling(e, 1)): begin / end of each, created on first use
-  double cov_ms[kCovKernels] = {0, 0, 0, 0};   // ... of the last pba_covariance, -1: the kernel did not run
+  KernelTimes<4> cov_times;         // k_cov_point, k_elim_pair, k_cov_invert, k_cov_points
 
   // camera prior (pba_set_camera_prior, pba_prior.h): one extra residual block on the camera blocks prior_slots, in information form
   bool prior_on = false;
@@ -198,17 +223,11 @@ struct pba_engine : pba::Handle {      // (device, stream, err, mem, events)
   double* d_prior = nullptr;        // x0 [6 k] | eta [6 k] | Lambda [6 k][6 k]
   double* d_prior_out = nullptr;    // [6 k + 1] gradient | E of the last evaluation that asked for them
   // marginalisation (pba_marginalize): everything on first use, nothing shared with the LM
-  double* d_marg_X = nullptr;       // [n_points][6] factor of V^-1, zero outside the marginalised points
   double* d_marg_z = nullptr;       // [n_points][3]
-  double* d_marg_part = nullptr;    // [point blocks][kMargPart]
-  double* d_marg_S = nullptr;       // [n][n] Schur complement of the marginalised points over every free camera
-  double* d_marg_r = nullptr;       // [n] its gradient
+  double* d_marg_r = nullptr;       // [n] gradient of the reduced system d_elim_S
   double* d_marg_L = nullptr;       // [nk][nk] the output
   double* d_marg_eta = nullptr;     // [nk]
-  double* d_marg_info = nullptr;    // [3] (k_marg_eliminate)
-  static constexpr int kMargKernels = 5;   // k_marg_point, k_marg_schur, k_marg_grad, k_prior, k_marg_eliminate
-  hipEvent_t marg_ev[2 * kMargKernels] = {};   // event profiling (pba_set_profiling(e, 1)), created on first use
-  double marg_ms[kMargKernels] = {0, 0, 0, 0, 0};   // ... of the last pba_marginalize, -1: the kernel did not run
+  KernelTimes<5> marg_times;        // k_marg_point, k_elim_pair, k_marg_grad, k_prior, k_marg_eliminate
 
   // outlier culling (pba_cull, pba_cull.h): everything on first use, nothing shared with the LM
   uint32_t* d_cull_hist = nullptr;  // [kCullPasses][kCullBins] radix-select tables
@@ -296,6 +315,40 @@ const double* rays_or_null(const pba_engine* e) { return e->inverse_depth ? e->d
 int check_lds(pba_engine* e, size_t need, const char* prefix, int count, const char* what, const char* use) {
   if (e->lds_max <= 0 || need <= (size_t)e->lds_max) return PBA_OK;
   return fail(e, PBA_ERR_INVALID, "%s%d %s need %zu bytes of LDS for %s, the device offers %d per workgroup", prefix, count, what, need, use, e->lds_max);
+}
+
+// ---- shared by the two off-loop calls that eliminate the points (pba_covariance, pba_marginalize) ---------------------------------------
+// The workgroup rows of a point kernel (pba_elim.h: smallest pivot | first failing point | n_sums sums, the cost first), read back
+// behind whatever the caller queued, the stream drained, and reduced in block order.
+struct PointPartials { double min_pivot = 1.0, sums[2] = {0.0, 0.0}; int32_t failed = -1; };
+int read_point_partials(pba_engine* e, int pt_blocks, int n_sums, PointPartials* out) {
+  const int width = elim_part_width(n_sums);
+  std::vector<double> part((size_t)width * pt_blocks);
+  HIP_TRY(e, hipMemcpyAsync(part.data(), e->d_elim_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  double bad = kElimNone;
+  for (int k = 0; k < pt_blocks; ++k) {      // block order
+    const double* row = part.data() + (size_t)width * k;
+    out->min_pivot = std::min(out->min_pivot, row[0]);
+    bad = std::min(bad, row[1]);
+    for (int i = 0; i < n_sums; ++i) out->sums[i] += row[2 + i];
+  }
+  if (bad < kElimNone) out->failed = (int32_t)bad;
+  return PBA_OK;
+}
+// a failing point block: the info fields and the PBA_ERR_NUMERIC report of `call`
+template <class Info>
+int point_block_failed(pba_engine* e, const char* call, const char* tail, int32_t point, Info& inf, Info* info) {
+  inf.failed_is_point = 1; inf.failed_index = point; inf.min_point_pivot = 0.0;
+  if (info) *info = inf;
+  return fail(e, PBA_ERR_NUMERIC, "%s: the block of point %d is not positive definite (non-positive or non-finite pivot)%s", call, point, tail);
+}
+// what the kernels of both calls read of the engine's current point
+template <class Params>
+void elim_inputs(const pba_engine* e, Params& p) {
+  const int cur = e->cur;
+  p.xyz = e->d_xyz[cur]; p.geom = e->d_geom[cur]; p.rec = e->d_rec[cur]; p.pt_begin = e->d_pt_begin; p.obs_slot = e->d_obs_slot;
+  p.rec_stride = e->rec_stride; p.n_points = e->n_points; p.fx = e->cfg.fx; p.fy = e->cfg.fy;
 }
 
 // ---- what is derived from what: a setter names the inputs it changed, invalidate() drops the caches derived from them; no setter
@@ -1946,7 +1999,7 @@ int pba_get_reduced_system(pba_engine* e, double* S, double* rhs, int32_t* n_out
 }
 
 // Covariance output (pba_cov.h).  Every refusal comes before the first launch; the Jacobian pass is pba_linearize's; the kernels write
-// covariance-owned buffers only, and the host copies the results out once every pivot is known to be positive.
+// buffers of the off-loop calls only, and the host copies the results out once every pivot is known to be positive.
 int pba_covariance(pba_engine* e, double* cam_cov, double* point_cov, pba_covariance_info* info) {
   if (!e) return PBA_ERR_INVALID;
   pba_covariance_info inf{};
@@ -1961,7 +2014,7 @@ int pba_covariance(pba_engine* e, double* cam_cov, double* point_cov, pba_covari
     return fail(e, PBA_ERR_INVALID, "pba_covariance: the cameras are constant (pba_set_cameras_constant): cam_cov must be NULL");
   { const int rc0 = check_ready(e, "pba_covariance"); if (rc0) return rc0; }
   // the program's camera columns in ascending slot order
-  CovSchurParams cs{};
+  ElimPairParams cs{};
   CovPointsParams cp{};
   int n_cols = 0;
   uint32_t cost_mask = 0xffffffffu;
@@ -1983,116 +2036,93 @@ int pba_covariance(pba_engine* e, double* cam_cov, double* point_cov, pba_covari
   }
   const int n = 6 * n_cols;
   const int dim = e->inverse_depth ? 1 : 3;
-  const int pt_blocks = (e->n_points + kCovThreads - 1) / kCovThreads;
+  const int pt_blocks = (e->n_points + kElimThreads - 1) / kElimThreads;
   PBA_ENTER(e);
   int rc;
   if (n > 0 && (rc = check_lds(e, cov_invert_smem_bytes(n) + 64, "pba_covariance: ", n_cols, "camera columns", "the inverse"))) return rc;
   if ((rc = pba_linearize(e, nullptr))) return rc;
-  const int cur = e->cur;
-  if ((rc = dev_alloc(e, &e->d_cov_part, (size_t)kCovPart * pt_blocks))) return rc;
+  if ((rc = dev_alloc(e, &e->d_elim_part, (size_t)kCovPart * pt_blocks))) return rc;
   if (!pose) {
     if ((rc = dev_alloc(e, &e->d_cov_P, (size_t)6 * e->n_points))) return rc;
-    if ((rc = dev_alloc(e, &e->d_cov_X, (size_t)6 * e->n_points))) return rc;
+    if ((rc = dev_alloc(e, &e->d_elim_X, (size_t)6 * e->n_points))) return rc;
     if ((rc = dev_alloc(e, &e->d_cov_pp, (size_t)9 * e->n_points))) return rc;
   }
   if (n > 0) {
-    if ((rc = dev_alloc(e, &e->d_cov_S, (size_t)n * n))) return rc;
+    if ((rc = dev_alloc(e, &e->d_elim_S, (size_t)n * n))) return rc;
     if ((rc = dev_alloc(e, &e->d_cov_C, (size_t)n * n))) return rc;
-    if ((rc = dev_alloc(e, &e->d_cov_info, (size_t)2))) return rc;
+    if ((rc = dev_alloc(e, &e->d_elim_info, (size_t)3))) return rc;
   }
   const double* rays = rays_or_null(e);
   CovPointParams pp{};
-  pp.xyz = e->d_xyz[cur]; pp.rays = rays; pp.geom = e->d_geom[cur]; pp.rec = e->d_rec[cur]; pp.pt_begin = e->d_pt_begin; pp.obs_slot = e->d_obs_slot;
-  pp.P = pose ? nullptr : e->d_cov_P; pp.X = pose ? nullptr : e->d_cov_X; pp.pp = structure ? e->d_cov_pp : nullptr; pp.part = e->d_cov_part; pp.rec_stride = e->rec_stride;
-  pp.n_points = e->n_points; pp.n_frames = e->n_frames; pp.dim = dim; pp.cost_mask = cost_mask; pp.fx = e->cfg.fx; pp.fy = e->cfg.fy;
-  // event profiling: one begin / end pair per kernel, read back at the end of the call (pba_internal_covariance_times)
-  const bool timed = e->profile;
-  bool ran[pba_engine::kCovKernels] = {false, false, false, false};
-  if (timed && !e->cov_ev[0])
-    for (int k = 0; k < 2 * pba_engine::kCovKernels; ++k) { if ((rc = handle_event(e, &e->cov_ev[k]))) return rc; }
-  auto mark = [&](int k, int end) { if (timed) { (void)hipEventRecord(e->cov_ev[2 * k + end], e->stream); ran[k] = true; } };
-  auto collect = [&]() {
-    for (int k = 0; k < pba_engine::kCovKernels; ++k) {
-      float ms = 0.0f;
-      e->cov_ms[k] = (timed && ran[k] && hipEventElapsedTime(&ms, e->cov_ev[2 * k], e->cov_ev[2 * k + 1]) == hipSuccess) ? (double)ms : -1.0;
-    }
-  };
-  mark(0, 0);
-  hipLaunchKernelGGL(k_cov_point, dim3(pt_blocks), dim3(kCovThreads), 0, e->stream, pp);
-  mark(0, 1);
+  elim_inputs(e, pp);
+  pp.rays = rays; pp.P = pose ? nullptr : e->d_cov_P; pp.X = pose ? nullptr : e->d_elim_X; pp.pp = structure ? e->d_cov_pp : nullptr; pp.part = e->d_elim_part;
+  pp.n_frames = e->n_frames; pp.dim = dim; pp.cost_mask = cost_mask;
+  // event profiling: read back at the end of the call (pba_internal_covariance_times)
+  KernelTimes<4>& times = e->cov_times;
+  if ((rc = times.start(e, e->profile))) return rc;
+  times.begin(e, 0);
+  hipLaunchKernelGGL(k_cov_point, dim3(pt_blocks), dim3(kElimThreads), 0, e->stream, pp);
+  times.end(e, 0);
   if (n > 0) {
-    cs.xyz = e->d_xyz[cur]; cs.rays = rays; cs.geom = e->d_geom[cur]; cs.rec = e->d_rec[cur]; cs.pt_begin = e->d_pt_begin; cs.obs_slot = e->d_obs_slot;
-    cs.X = pose ? nullptr : e->d_cov_X; cs.S = e->d_cov_S; cs.rec_stride = e->rec_stride;
-    cs.n_points = e->n_points; cs.n_frames = e->n_frames; cs.n_cols = n_cols; cs.fx = e->cfg.fx; cs.fy = e->cfg.fy;
+    elim_inputs(e, cs);
+    cs.rays = rays; cs.X = pose ? nullptr : e->d_elim_X; cs.S = e->d_elim_S; cs.n_cols = n_cols;
     // pose-only mode: S = blockdiag(U_a), the zero blocks by a memset and one workgroup per diagonal block
     cs.diag_only = pose ? 1 : 0;
-    mark(1, 0);
-    if (pose) HIP_TRY(e, hipMemsetAsync(e->d_cov_S, 0, sizeof(double) * n * n, e->stream));
-    hipLaunchKernelGGL(k_cov_schur, dim3(pose ? n_cols : n_cols * (n_cols + 1) / 2), dim3(kCovThreads), 0, e->stream, cs);
-    mark(1, 1);
+    times.begin(e, 1);
+    if (pose) HIP_TRY(e, hipMemsetAsync(e->d_elim_S, 0, sizeof(double) * n * n, e->stream));
+    hipLaunchKernelGGL(k_elim_pair<false>, dim3(pose ? n_cols : n_cols * (n_cols + 1) / 2), dim3(kElimThreads), 0, e->stream, cs);
+    times.end(e, 1);
     CovInvertParams ci{};
-    ci.S = e->d_cov_S; ci.C = e->d_cov_C; ci.info = e->d_cov_info; ci.n = n;
+    ci.S = e->d_elim_S; ci.C = e->d_cov_C; ci.info = e->d_elim_info; ci.n = n;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cov_invert), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cov_invert_smem_bytes(n));
     (void)hipGetLastError();
-    mark(2, 0);
+    times.begin(e, 2);
     hipLaunchKernelGGL(k_cov_invert, dim3(1), dim3(kCovInvertT), cov_invert_smem_bytes(n), e->stream, ci);
-    mark(2, 1);
+    times.end(e, 2);
   }
   // the first pass decides: nothing is launched on the inverse of a singular matrix, nothing is copied out
-  std::vector<double> part((size_t)kCovPart * pt_blocks);
   double cinfo[2] = {1.0, -1.0};
   HIP_TRY(e, hipGetLastError());
-  HIP_TRY(e, hipMemcpyAsync(part.data(), e->d_cov_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, e->stream));
-  if (n > 0) HIP_TRY(e, hipMemcpyAsync(cinfo, e->d_cov_info, sizeof(cinfo), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(e, hipStreamSynchronize(e->stream));
-  double cost = 0.0, bad_pt = kCovNone;
-  for (int k = 0; k < pt_blocks; ++k) {      // block order
-    inf.min_point_pivot = std::min(inf.min_point_pivot, part[(size_t)kCovPart * k]);
-    bad_pt = std::min(bad_pt, part[(size_t)kCovPart * k + 1]);
-    cost += part[(size_t)kCovPart * k + 2];
-  }
+  if (n > 0) HIP_TRY(e, hipMemcpyAsync(cinfo, e->d_elim_info, sizeof(cinfo), hipMemcpyDeviceToHost, e->stream));
+  PointPartials pts;
+  if ((rc = read_point_partials(e, pt_blocks, 1, &pts))) return rc;
+  inf.min_point_pivot = pts.min_pivot;
   inf.n_cam = n;
   inf.point_dim = pose ? 0 : dim;
   inf.num_residuals = (int32_t)(pba_internal_program_blocks(e) * pba_internal_patch_len(e));
   inf.num_parameters = n + (pose ? 0 : dim * e->n_points);
-  inf.cost = cost;
+  inf.cost = pts.sums[0];
   inf.min_cam_pivot = n > 0 ? cinfo[0] : 1.0;
-  if (bad_pt < kCovNone) {
-    collect();
-    inf.failed_is_point = 1; inf.failed_index = (int32_t)bad_pt; inf.min_point_pivot = 0.0;
-    if (info) *info = inf;
-    return fail(e, PBA_ERR_NUMERIC, "pba_covariance: the block of point %d is not positive definite (non-positive or non-finite pivot): "
-                                    "the normal matrix is singular", inf.failed_index);
+  if (pts.failed >= 0) {
+    times.collect();
+    return point_block_failed(e, "pba_covariance", ": the normal matrix is singular", pts.failed, inf, info);
   }
   if (n > 0 && cinfo[1] >= 0.0) {
-    collect();
+    times.collect();
     inf.failed_is_point = 0; inf.failed_index = (int32_t)cinfo[1];
     if (info) *info = inf;
     return fail(e, PBA_ERR_NUMERIC, "pba_covariance: non-positive or non-finite pivot at camera column %d (slot %d, parameter %d): the "
                                     "normal matrix is singular; is the gauge fixed?", inf.failed_index, (int)cs.slot_of_col[inf.failed_index / 6], inf.failed_index % 6);
   }
   if (point_cov && !pose && !structure) {
-    cp.xyz = e->d_xyz[cur]; cp.geom = e->d_geom[cur]; cp.rec = e->d_rec[cur]; cp.pt_begin = e->d_pt_begin; cp.obs_slot = e->d_obs_slot;
-    cp.P = e->d_cov_P; cp.C = e->d_cov_C; cp.pp = e->d_cov_pp; cp.rec_stride = e->rec_stride;
-    cp.n_points = e->n_points; cp.n_frames = e->n_frames; cp.n = n; cp.fx = e->cfg.fx; cp.fy = e->cfg.fy;
-    mark(3, 0);
-    hipLaunchKernelGGL(k_cov_points, dim3(pt_blocks), dim3(kCovThreads), 0, e->stream, cp);
-    mark(3, 1);
+    elim_inputs(e, cp);
+    cp.P = e->d_cov_P; cp.C = e->d_cov_C; cp.pp = e->d_cov_pp; cp.n_frames = e->n_frames; cp.n = n;
+    times.begin(e, 3);
+    hipLaunchKernelGGL(k_cov_points, dim3(pt_blocks), dim3(kElimThreads), 0, e->stream, cp);
+    times.end(e, 3);
     HIP_TRY(e, hipGetLastError());
   }
   if (cam_cov) HIP_TRY(e, hipMemcpyAsync(cam_cov, e->d_cov_C, sizeof(double) * n * n, hipMemcpyDeviceToHost, e->stream));
   if (point_cov) HIP_TRY(e, hipMemcpyAsync(point_cov, e->d_cov_pp, sizeof(double) * 9 * e->n_points, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));
-  collect();
+  times.collect();
   if (info) *info = inf;
   return PBA_OK;
 }
 
-// Event time [ms] of the four kernels of the LAST pba_covariance (k_cov_point, k_cov_schur with its memset in the pose-only mode,
+// Event time [ms] of the four kernels of the LAST pba_covariance (k_cov_point, k_elim_pair with its memset in the pose-only mode,
 // k_cov_invert, k_cov_points), -1 for a kernel that did not run or when event profiling (pba_set_profiling(e, 1)) was off.
-void pba_internal_covariance_times(const pba_engine* e, double* ms4) {
-  for (int k = 0; k < pba_engine::kCovKernels; ++k) ms4[k] = e->cov_ms[k];
-}
+void pba_internal_covariance_times(const pba_engine* e, double* ms4) { e->cov_times.copy_to(ms4); }
 
 // ---- camera prior (pba_prior.h) ---------------------------------------------------------------------------------------------------
 int pba_set_camera_prior(pba_engine* e, int32_t k, const int32_t* slots, const double* x0, const double* Lambda, const double* eta, double c) {
@@ -2137,7 +2167,8 @@ int pba_set_camera_prior(pba_engine* e, int32_t k, const int32_t* slots, const d
 }
 
 // Marginalisation (pba_prior.h).  Every refusal comes before the first launch; the Jacobian pass is pba_linearize's; the kernels write
-// marginalisation-owned buffers only, and the host copies the results out once every pivot is known to be positive.
+// buffers of the off-loop calls only (the d_elim_* set is shared with pba_covariance: either call writes all it reads of it), and
+// the host copies the results out once every pivot is known to be positive.
 int pba_marginalize(pba_engine* e, uint32_t drop_mask, int32_t* slots, double* x0, double* Lambda, double* eta, double* c, pba_marginal_info* info) {
   if (!e) return PBA_ERR_INVALID;
   pba_marginal_info inf{};
@@ -2151,7 +2182,7 @@ int pba_marginalize(pba_engine* e, uint32_t drop_mask, int32_t* slots, double* x
   if (e->n_frames < 32 && (drop_mask >> e->n_frames))
     return fail(e, PBA_ERR_INVALID, "pba_marginalize: drop_mask 0x%x has bits at or above n_frames = %d", drop_mask, e->n_frames);
   // camera columns of the elimination: every free slot in ascending order (the reduced program's columns), split into dropped and kept
-  MargSchurParams ms{};
+  ElimPairParams ms{};
   MargEliminateParams me{};
   int nd_cams = 0, nk_cams = 0;
   int32_t kept_slots[kMaxFrames];
@@ -2171,84 +2202,61 @@ int pba_marginalize(pba_engine* e, uint32_t drop_mask, int32_t* slots, double* x
     if (in) { ++inf.n_points; inf.n_blocks += e->h_pt_begin[p + 1] - e->h_pt_begin[p]; }
   }
   inf.k = nk_cams;
-  const int pt_blocks = (e->n_points + kCovThreads - 1) / kCovThreads;
+  const int pt_blocks = (e->n_points + kElimThreads - 1) / kElimThreads;
   PBA_ENTER(e);
   int rc;
   if ((rc = check_lds(e, marg_eliminate_smem_bytes(nd, nk) + 64, "pba_marginalize: ", nd_cams, "dropped free cameras", "their elimination"))) return rc;
   if ((rc = pba_linearize(e, nullptr))) return rc;
-  const int cur = e->cur;
-  if ((rc = dev_alloc(e, &e->d_marg_X, (size_t)6 * e->n_points))) return rc;
+  if ((rc = dev_alloc(e, &e->d_elim_X, (size_t)6 * e->n_points))) return rc;
   if ((rc = dev_alloc(e, &e->d_marg_z, (size_t)3 * e->n_points))) return rc;
-  if ((rc = dev_alloc(e, &e->d_marg_part, (size_t)kMargPart * pt_blocks))) return rc;
-  if ((rc = dev_alloc(e, &e->d_marg_S, (size_t)n * n))) return rc;
+  if ((rc = dev_alloc(e, &e->d_elim_part, (size_t)kMargPart * pt_blocks))) return rc;
+  if ((rc = dev_alloc(e, &e->d_elim_S, (size_t)n * n))) return rc;
   if ((rc = dev_alloc(e, &e->d_marg_r, (size_t)n))) return rc;
   if ((rc = dev_alloc(e, &e->d_marg_L, (size_t)nk * nk))) return rc;
   if ((rc = dev_alloc(e, &e->d_marg_eta, (size_t)nk))) return rc;
-  if ((rc = dev_alloc(e, &e->d_marg_info, (size_t)3))) return rc;
-  const bool timed = e->profile;
-  bool ran[pba_engine::kMargKernels] = {false, false, false, false, false};
-  if (timed && !e->marg_ev[0])
-    for (int k = 0; k < 2 * pba_engine::kMargKernels; ++k) { if ((rc = handle_event(e, &e->marg_ev[k]))) return rc; }
-  auto mark = [&](int k, int end) { if (timed) { (void)hipEventRecord(e->marg_ev[2 * k + end], e->stream); ran[k] = true; } };
-  auto collect = [&]() {
-    for (int k = 0; k < pba_engine::kMargKernels; ++k) {
-      float t = 0.0f;
-      e->marg_ms[k] = (timed && ran[k] && hipEventElapsedTime(&t, e->marg_ev[2 * k], e->marg_ev[2 * k + 1]) == hipSuccess) ? (double)t : -1.0;
-    }
-  };
+  if ((rc = dev_alloc(e, &e->d_elim_info, (size_t)3))) return rc;
+  KernelTimes<5>& times = e->marg_times;
+  if ((rc = times.start(e, e->profile))) return rc;
   MargPointParams mp{};
-  mp.xyz = e->d_xyz[cur]; mp.geom = e->d_geom[cur]; mp.rec = e->d_rec[cur]; mp.pt_begin = e->d_pt_begin; mp.obs_slot = e->d_obs_slot;
-  mp.X = e->d_marg_X; mp.z = e->d_marg_z; mp.part = e->d_marg_part; mp.rec_stride = e->rec_stride;
-  mp.n_points = e->n_points; mp.n_frames = e->n_frames; mp.drop_mask = drop_mask; mp.fx = e->cfg.fx; mp.fy = e->cfg.fy;
-  mark(0, 0);
-  hipLaunchKernelGGL(k_marg_point, dim3(pt_blocks), dim3(kCovThreads), 0, e->stream, mp);
-  mark(0, 1);
-  ms.xyz = e->d_xyz[cur]; ms.geom = e->d_geom[cur]; ms.rec = e->d_rec[cur]; ms.pt_begin = e->d_pt_begin; ms.obs_slot = e->d_obs_slot;
-  ms.X = e->d_marg_X; ms.z = e->d_marg_z; ms.S = e->d_marg_S; ms.r = e->d_marg_r; ms.rec_stride = e->rec_stride;
-  ms.n_points = e->n_points; ms.n_cols = n_cols; ms.drop_mask = drop_mask; ms.fx = e->cfg.fx; ms.fy = e->cfg.fy;
-  mark(1, 0);
-  hipLaunchKernelGGL(k_marg_schur, dim3(n_cols * (n_cols + 1) / 2), dim3(kCovThreads), 0, e->stream, ms);
-  mark(1, 1);
-  mark(2, 0);
-  hipLaunchKernelGGL(k_marg_grad, dim3(n_cols), dim3(kCovThreads), 0, e->stream, ms);
-  mark(2, 1);
+  elim_inputs(e, mp);
+  mp.X = e->d_elim_X; mp.z = e->d_marg_z; mp.part = e->d_elim_part; mp.n_frames = e->n_frames; mp.drop_mask = drop_mask;
+  times.begin(e, 0);
+  hipLaunchKernelGGL(k_marg_point, dim3(pt_blocks), dim3(kElimThreads), 0, e->stream, mp);
+  times.end(e, 0);
+  elim_inputs(e, ms);
+  ms.X = e->d_elim_X; ms.z = e->d_marg_z; ms.S = e->d_elim_S; ms.r = e->d_marg_r; ms.n_cols = n_cols; ms.point_mask = drop_mask;
+  times.begin(e, 1);
+  hipLaunchKernelGGL(k_elim_pair<true>, dim3(n_cols * (n_cols + 1) / 2), dim3(kElimThreads), 0, e->stream, ms);
+  times.end(e, 1);
+  times.begin(e, 2);
+  hipLaunchKernelGGL(k_marg_grad, dim3(n_cols), dim3(kElimThreads), 0, e->stream, ms);
+  times.end(e, 2);
   if (e->prior_on) {
     // the current prior is one more factor: re-expanded at the current cameras (exact: it is quadratic), so priors chain
-    PriorParams pp = prior_params(e, e->d_cams[cur]);
-    pp.S = e->d_marg_S; pp.r = e->d_marg_r; pp.ld = n; pp.out = e->d_prior_out;
-    mark(3, 0);
+    PriorParams pp = prior_params(e, e->d_cams[e->cur]);
+    pp.S = e->d_elim_S; pp.r = e->d_marg_r; pp.ld = n; pp.out = e->d_prior_out;
+    times.begin(e, 3);
     launch_prior(e, pp);
-    mark(3, 1);
+    times.end(e, 3);
   }
-  me.S = e->d_marg_S; me.r = e->d_marg_r; me.Lambda = e->d_marg_L; me.eta = e->d_marg_eta; me.info = e->d_marg_info;
+  me.S = e->d_elim_S; me.r = e->d_marg_r; me.Lambda = e->d_marg_L; me.eta = e->d_marg_eta; me.info = e->d_elim_info;
   me.n = n; me.nd_cams = nd_cams; me.nk_cams = nk_cams;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_marg_eliminate), hipFuncAttributeMaxDynamicSharedMemorySize, (int)marg_eliminate_smem_bytes(nd, nk));
   (void)hipGetLastError();
-  mark(4, 0);
+  times.begin(e, 4);
   hipLaunchKernelGGL(k_marg_eliminate, dim3(1), dim3(kMargElimThreads), marg_eliminate_smem_bytes(nd, nk), e->stream, me);
-  mark(4, 1);
+  times.end(e, 4);
   HIP_TRY(e, hipGetLastError());
-  std::vector<double> part((size_t)kMargPart * pt_blocks);
   double einfo[3] = {1.0, -1.0, 0.0}, E_old = 0.0;
-  HIP_TRY(e, hipMemcpyAsync(part.data(), e->d_marg_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(e, hipMemcpyAsync(einfo, e->d_marg_info, sizeof(einfo), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(einfo, e->d_elim_info, sizeof(einfo), hipMemcpyDeviceToHost, e->stream));
   if (e->prior_on) HIP_TRY(e, hipMemcpyAsync(&E_old, e->d_prior_out + 6 * e->prior_k, sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(e, hipStreamSynchronize(e->stream));
-  collect();
-  double cost = 0.0, zz = 0.0, bad_pt = kCovNone;
-  for (int k = 0; k < pt_blocks; ++k) {      // block order
-    inf.min_point_pivot = std::min(inf.min_point_pivot, part[(size_t)kMargPart * k]);
-    bad_pt = std::min(bad_pt, part[(size_t)kMargPart * k + 1]);
-    cost += part[(size_t)kMargPart * k + 2];
-    zz += part[(size_t)kMargPart * k + 3];
-  }
-  inf.cost = cost;
+  PointPartials pts;
+  if ((rc = read_point_partials(e, pt_blocks, 2, &pts))) return rc;
+  times.collect();
+  inf.min_point_pivot = pts.min_pivot;
+  inf.cost = pts.sums[0];
   inf.min_cam_pivot = einfo[0];
-  if (bad_pt < kCovNone) {
-    inf.failed_is_point = 1; inf.failed_index = (int32_t)bad_pt; inf.min_point_pivot = 0.0;
-    if (info) *info = inf;
-    return fail(e, PBA_ERR_NUMERIC, "pba_marginalize: the block of point %d is not positive definite (non-positive or non-finite pivot)", inf.failed_index);
-  }
+  if (pts.failed >= 0) return point_block_failed(e, "pba_marginalize", "", pts.failed, inf, info);
   if (einfo[1] >= 0.0) {
     inf.failed_is_point = 0; inf.failed_index = (int32_t)einfo[1];
     if (info) *info = inf;
@@ -2265,16 +2273,14 @@ int pba_marginalize(pba_engine* e, uint32_t drop_mask, int32_t* slots, double* x
     slots[i] = kept_slots[i];
     std::memcpy(x0 + 6 * i, cams.data() + 6 * kept_slots[i], sizeof(double) * 6);
   }
-  *c = ((cost - zz) - einfo[2]) + E_old;
+  *c = ((pts.sums[0] - pts.sums[1]) - einfo[2]) + E_old;      // (sums: cost_M | sum over M of |z|^2 / 2)
   if (info) *info = inf;
   return PBA_OK;
 }
 
-// Event time [ms] of the five kernels of the LAST pba_marginalize (k_marg_point, k_marg_schur, k_marg_grad, k_prior, k_marg_eliminate),
+// Event time [ms] of the five kernels of the LAST pba_marginalize (k_marg_point, k_elim_pair, k_marg_grad, k_prior, k_marg_eliminate),
 // -1 for a kernel that did not run or when event profiling (pba_set_profiling(e, 1)) was off.
-void pba_internal_marginal_times(const pba_engine* e, double* ms5) {
-  for (int k = 0; k < pba_engine::kMargKernels; ++k) ms5[k] = e->marg_ms[k];
-}
+void pba_internal_marginal_times(const pba_engine* e, double* ms5) { e->marg_times.copy_to(ms5); }
 
 // ---- outlier culling (pba_cull.h) -------------------------------------------------------------------------------------------------
 int pba_get_block_costs(pba_engine* e, double* cost) {

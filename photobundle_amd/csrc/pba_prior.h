@@ -8,17 +8,17 @@
 //                    dense system (pba_marginalize), and / or E to a scalar (the candidate cost), and / or writes g | E out
 // The marginalisation eliminates the points M that the dropped slots see, then the free dropped cameras, from the undamped, unscaled
 // normal equations of M's residual blocks (plus the current prior):
-//   k_marg_point     one lane per point of M: V, g_p, the equilibrated 3x3 Cholesky factor X of V^-1 (the arithmetic of k_cov_point),
+//   k_marg_point     one lane per point of M: V, g_p, the equilibrated 3x3 Cholesky factor X of V^-1 (elim_factor_point's arithmetic),
 //                    z = X g_p; per workgroup the smallest pivot, the first failing point, the cost of M's blocks, |z|^2 / 2
-//   k_marg_schur     one workgroup per pair of free camera columns: the pair block of U - sum_M W P W^T (k_cov_schur restricted to M;
-//                    pba_cov.h itself stays as it is, so that pba_covariance keeps its bits)
+//   k_elim_pair      (pba_elim.h) one workgroup per pair of free camera columns: the pair block of U - sum_M W P W^T, the points of M
+//                    selected by the mask of the dropped slots
 //   k_marg_grad      one workgroup per free camera column: g_c - sum_M W V^-1 g_p = -sum Ac^T (b + G z)
 //   k_marg_eliminate ONE workgroup: unit-diagonal Cholesky of the dropped cameras' block S_DD, Y = L^-1 D^-1/2 [S_DK | r_D],
 //                    Lambda = S_KK - Y^T Y (lower triangle computed, mirrored), eta = r_K - Y^T y, |y|^2 / 2
 // Every sum has a fixed order; there are no floating-point atomics: two fresh engines give the same bits.
 // Included by pba_engine.hip after pba_cov.h.
 #pragma once
-#include "pba_cov.h"
+#include "pba_elim.h"
 
 namespace pba {
 
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(kPriorThreads) void k_prior(PriorParams p) {
 // =====================================================================================================
 // marginalisation
 // =====================================================================================================
-constexpr int kMargPart = 4;           // per workgroup of k_marg_point: smallest pivot | first failing point (kCovNone) | cost | |z|^2 / 2
+constexpr int kMargPart = elim_part_width(2);      // per workgroup of k_marg_point: smallest pivot | first failing point | cost | |z|^2 / 2
 
 struct MargPointParams {
   const double* xyz;
@@ -114,36 +114,30 @@ struct MargPointParams {
   double* part;                  // [gridDim.x][kMargPart]
   int64_t rec_stride;
   int32_t n_points, n_frames;
-  uint32_t drop_mask;
+  uint32_t drop_mask;            // the point is in M: one of its observations is in a dropped slot
   double fx, fy;
 };
 
-// the point is in M: one of its observations is in a dropped slot
-__device__ __forceinline__ bool marg_in_set(const uint8_t* __restrict__ obs_slot, int o0, int o1, uint32_t drop_mask) {
-  bool in = false;
-  for (int o = o0; o < o1; ++o) in = in || ((drop_mask >> obs_slot[o]) & 1u);
-  return in;
-}
-
-__global__ __launch_bounds__(kCovThreads) void k_marg_point(MargPointParams p) {
+__global__ __launch_bounds__(kElimThreads) void k_marg_point(MargPointParams p) {
   __shared__ CamGeom s_geom[kMaxFrames];
-  __shared__ double s_red[kCovWaves][kMargPart];
   const int tid = threadIdx.x;
-  stage_geom<kCovThreads, false, kMaxFrames>(p.geom, s_geom, p.n_frames, tid);
+  stage_geom<kElimThreads, false, kMaxFrames>(p.geom, s_geom, p.n_frames, tid);
   __syncthreads();
-  const int pt = blockIdx.x * kCovThreads + tid;
-  double piv = 1.0, bad = kCovNone, cost = 0.0, zz = 0.0;
+  const int pt = blockIdx.x * kElimThreads + tid;
+  double piv = 1.0, bad = kElimNone, cost = 0.0, zz = 0.0;
   if (pt < p.n_points) {
     const int o0 = p.pt_begin[pt], o1 = p.pt_begin[pt + 1];
     double Xm[6] = {0, 0, 0, 0, 0, 0}, zv[3] = {0, 0, 0};
-    if (marg_in_set(p.obs_slot, o0, o1, p.drop_mask)) {
+    if (elim_in_set(p.obs_slot, o0, o1, p.drop_mask)) {
       const double X[3] = {p.xyz[3 * (size_t)pt], p.xyz[3 * (size_t)pt + 1], p.xyz[3 * (size_t)pt + 2]};
       double V[6] = {0, 0, 0, 0, 0, 0}, gp[3] = {0, 0, 0};
       for (int o = o0; o < o1; ++o) {      // list order
         cost += p.rec[5 * p.rec_stride + o];
         double Ac[2][6], MAp[2][3], Ap[2][3], M[3];
-        cov_observation(s_geom[p.obs_slot[o]], X, nullptr, nullptr, p.rec, p.rec_stride, o, p.fx, p.fy, Ac, MAp, Ap, M);
+        elim_observation(s_geom[p.obs_slot[o]], X, nullptr, nullptr, p.rec, p.rec_stride, o, p.fx, p.fy, Ac, MAp, Ap, M);
         const double b0 = p.rec[3 * p.rec_stride + o], b1 = p.rec[4 * p.rec_stride + o];
+        // (elim_add_point_block, written out: through the function this kernel is allocated 64 registers instead of 70 and its other
+        // code runs 0.76 us longer at 5 000 and at 50 000 points, profiles/refactor/elimination_ab_timing.txt)
         V[0] += Ap[0][0] * MAp[0][0] + Ap[1][0] * MAp[1][0];
         V[1] += Ap[0][0] * MAp[0][1] + Ap[1][0] * MAp[1][1];
         V[2] += Ap[0][0] * MAp[0][2] + Ap[1][0] * MAp[1][2];
@@ -153,16 +147,18 @@ __global__ __launch_bounds__(kCovThreads) void k_marg_point(MargPointParams p) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) gp[k] -= Ap[0][k] * b0 + Ap[1][k] * b1;      // g = -A^T b
       }
-      // unit-diagonal block: a10 a20 a21 are correlations, the pivots are 1, d1, d2 (k_cov_point's factorisation)
-      bool ok = cov_pivot_ok(V[0]) && cov_pivot_ok(V[3]) && cov_pivot_ok(V[5]);
+      // elim_factor_point's arithmetic, written out: with the shared function in its place (z formed here or inside it, with or without
+      // its inverse) the compiler's code for this kernel gives another z, and the reduced gradient and eta move in their last bits against
+      // tests/golden/elimination_bits.json.  A change to the factorisation is made in both places.
+      bool ok = elim_pivot_ok(V[0]) && elim_pivot_ok(V[3]) && elim_pivot_ok(V[5]);
       const double e0 = 1.0 / sqrt(ok ? V[0] : 1.0), e1 = 1.0 / sqrt(ok ? V[3] : 1.0), e2 = 1.0 / sqrt(ok ? V[5] : 1.0);
       const double l10 = V[1] * e0 * e1, l20 = V[2] * e0 * e2, a21 = V[4] * e1 * e2;
       const double d1 = 1.0 - l10 * l10;
-      ok = ok && cov_pivot_ok(d1);
+      ok = ok && elim_pivot_ok(d1);
       const double l11 = sqrt(ok ? d1 : 1.0);
       const double l21 = (a21 - l20 * l10) / l11;
       const double d2 = 1.0 - l20 * l20 - l21 * l21;
-      ok = ok && cov_pivot_ok(d2);
+      ok = ok && elim_pivot_ok(d2);
       const double l22 = sqrt(ok ? d2 : 1.0);
       if (ok) {
         piv = fmin(d1, d2);
@@ -184,131 +180,23 @@ __global__ __launch_bounds__(kCovThreads) void k_marg_point(MargPointParams p) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) p.z[3 * (size_t)pt + k] = zv[k];
   }
-  // workgroup partials: butterfly per wave, the waves in order
-  piv = wave_min(piv); bad = wave_min(bad); cost = wave_sum(cost); zz = wave_sum(zz);
-  if ((tid & 63) == 0) { s_red[tid >> 6][0] = piv; s_red[tid >> 6][1] = bad; s_red[tid >> 6][2] = cost; s_red[tid >> 6][3] = zz; }
-  __syncthreads();
-  if (tid == 0) {
-    double m = s_red[0][0], b = s_red[0][1], c = s_red[0][2], q = s_red[0][3];
-    for (int w = 1; w < kCovWaves; ++w) { m = fmin(m, s_red[w][0]); b = fmin(b, s_red[w][1]); c += s_red[w][2]; q += s_red[w][3]; }
-    double* o4 = p.part + kMargPart * (size_t)blockIdx.x;
-    o4[0] = m; o4[1] = b; o4[2] = c; o4[3] = q;
-  }
-}
-
-struct MargSchurParams {
-  const double* xyz;
-  const CamGeom* geom;
-  const double* rec;
-  const int32_t* pt_begin;
-  const uint8_t* obs_slot;
-  const double* X;               // [n_points][6] (k_marg_point)
-  const double* z;               // [n_points][3]
-  double* S;                     // [n][n] row-major, n = 6 n_cols, both triangles from the one computed value
-  double* r;                     // [n] reduced gradient
-  int64_t rec_stride;
-  int32_t n_points, n_cols;
-  uint32_t drop_mask;
-  double fx, fy;
-  uint8_t slot_of_col[kMaxFrames];
-};
-
-// Workgroup q: the pair (a, b), a <= b, of camera columns enumerated row by row.  k_cov_schur's walk and sums (per lane in point order,
-// butterfly per wave, the waves in order) over the points of M only.
-__global__ __launch_bounds__(kCovThreads) void k_marg_schur(MargSchurParams p) {
-  __shared__ CamGeom s_geom[2];
-  __shared__ double s_red[kCovWaves][36];
-  const int tid = threadIdx.x;
-  const int nc = p.n_cols, n = 6 * nc;
-  int a = 0, rem = blockIdx.x;
-  while (rem >= nc - a) { rem -= nc - a; ++a; }
-  const int b = a + rem;
-  const int sa = p.slot_of_col[a], sb = p.slot_of_col[b];
-  if (tid == 0) { s_geom[0] = p.geom[sa]; s_geom[1] = p.geom[sb]; }
-  __syncthreads();
-  double acc[36];
-#pragma unroll
-  for (int k = 0; k < 36; ++k) acc[k] = 0.0;
-  for (int pt = tid; pt < p.n_points; pt += kCovThreads) {
-    const int o0 = p.pt_begin[pt], o1 = p.pt_begin[pt + 1];
-    bool seen_a = false, seen_b = false;
-    for (int o = o0; o < o1; ++o) { const int s = p.obs_slot[o]; seen_a = seen_a || s == sa; seen_b = seen_b || s == sb; }
-    if (!seen_a || !seen_b || !marg_in_set(p.obs_slot, o0, o1, p.drop_mask)) continue;
-    const double X[3] = {p.xyz[3 * (size_t)pt], p.xyz[3 * (size_t)pt + 1], p.xyz[3 * (size_t)pt + 2]};
-    double Xm[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) Xm[k] = p.X[6 * (size_t)pt + k];
-    for (int l = o0; l < o1; ++l) {
-      if (p.obs_slot[l] != sa) continue;
-      double Aca[2][6], MApa[2][3], Apa[2][3], Ma[3];
-      cov_observation(s_geom[0], X, nullptr, nullptr, p.rec, p.rec_stride, l, p.fx, p.fy, Aca, MApa, Apa, Ma);
-      if (a == b) {
-        double MAc[2][6];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) { MAc[0][j] = Ma[0] * Aca[0][j] + Ma[1] * Aca[1][j]; MAc[1][j] = Ma[1] * Aca[0][j] + Ma[2] * Aca[1][j]; }
-#pragma unroll
-        for (int i = 0; i < 6; ++i)
-#pragma unroll
-          for (int j = 0; j < 6; ++j) acc[6 * i + j] += Aca[0][i] * MAc[0][j] + Aca[1][i] * MAc[1][j];
-      }
-      double Ga[2][3];
-      cov_times_factor(MApa, Xm, Ga);
-      for (int m = o0; m < o1; ++m) {
-        if (p.obs_slot[m] != sb) continue;
-        double Acb[2][6], MApb[2][3], Apb[2][3], Mb[3];
-        cov_observation(s_geom[1], X, nullptr, nullptr, p.rec, p.rec_stride, m, p.fx, p.fy, Acb, MApb, Apb, Mb);
-        double Gb[2][3], N[2][2], Z[2][6];
-        cov_times_factor(MApb, Xm, Gb);
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-#pragma unroll
-          for (int t = 0; t < 2; ++t) N[r][t] = Ga[r][0] * Gb[t][0] + Ga[r][1] * Gb[t][1] + Ga[r][2] * Gb[t][2];
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-#pragma unroll
-          for (int j = 0; j < 6; ++j) Z[r][j] = N[r][0] * Acb[0][j] + N[r][1] * Acb[1][j];
-#pragma unroll
-        for (int i = 0; i < 6; ++i)
-#pragma unroll
-          for (int j = 0; j < 6; ++j) acc[6 * i + j] -= Aca[0][i] * Z[0][j] + Aca[1][i] * Z[1][j];
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 36; ++k) {
-    const double v = wave_sum(acc[k]);
-    if ((tid & 63) == 0) s_red[tid >> 6][k] = v;
-  }
-  __syncthreads();
-  if (tid < 36) {
-    double v = s_red[0][tid];
-#pragma unroll
-    for (int w = 1; w < kCovWaves; ++w) v += s_red[w][tid];
-    const int i = tid / 6, j = tid - 6 * i;
-    if (a != b) {
-      p.S[(size_t)(6 * a + i) * n + 6 * b + j] = v;
-      p.S[(size_t)(6 * b + j) * n + 6 * a + i] = v;
-    } else if (i >= j) {
-      p.S[(size_t)(6 * a + i) * n + 6 * a + j] = v;
-      p.S[(size_t)(6 * a + j) * n + 6 * a + i] = v;
-    }
-  }
+  elim_point_partial<2>(piv, bad, cost, zz, p.part + kMargPart * (size_t)blockIdx.x);
 }
 
 // Workgroup a: the reduced gradient of camera column a over the points of M, r_a = sum_l -Ac_l^T (b_l + G_l z), G_l = (M Ap)_l X^T
-__global__ __launch_bounds__(kCovThreads) void k_marg_grad(MargSchurParams p) {
+__global__ __launch_bounds__(kElimThreads) void k_marg_grad(ElimPairParams p) {
   __shared__ CamGeom s_geom;
-  __shared__ double s_red[kCovWaves][6];
+  __shared__ double s_red[kElimWaves][6];
   const int tid = threadIdx.x;
   const int a = blockIdx.x, sa = p.slot_of_col[a];
   if (tid == 0) s_geom = p.geom[sa];
   __syncthreads();
   double acc[6] = {0, 0, 0, 0, 0, 0};
-  for (int pt = tid; pt < p.n_points; pt += kCovThreads) {
+  for (int pt = tid; pt < p.n_points; pt += kElimThreads) {
     const int o0 = p.pt_begin[pt], o1 = p.pt_begin[pt + 1];
     bool seen = false;
     for (int o = o0; o < o1; ++o) seen = seen || p.obs_slot[o] == sa;
-    if (!seen || !marg_in_set(p.obs_slot, o0, o1, p.drop_mask)) continue;
+    if (!seen || !elim_in_set(p.obs_slot, o0, o1, p.point_mask)) continue;
     const double X[3] = {p.xyz[3 * (size_t)pt], p.xyz[3 * (size_t)pt + 1], p.xyz[3 * (size_t)pt + 2]};
     double Xm[6];
 #pragma unroll
@@ -317,8 +205,8 @@ __global__ __launch_bounds__(kCovThreads) void k_marg_grad(MargSchurParams p) {
     for (int l = o0; l < o1; ++l) {
       if (p.obs_slot[l] != sa) continue;
       double Ac[2][6], MAp[2][3], Ap[2][3], M[3], G[2][3];
-      cov_observation(s_geom, X, nullptr, nullptr, p.rec, p.rec_stride, l, p.fx, p.fy, Ac, MAp, Ap, M);
-      cov_times_factor(MAp, Xm, G);
+      elim_observation(s_geom, X, nullptr, nullptr, p.rec, p.rec_stride, l, p.fx, p.fy, Ac, MAp, Ap, M);
+      elim_times_factor(MAp, Xm, G);
       const double t0 = p.rec[3 * p.rec_stride + l] + (G[0][0] * z0 + G[0][1] * z1 + G[0][2] * z2);
       const double t1 = p.rec[4 * p.rec_stride + l] + (G[1][0] * z0 + G[1][1] * z1 + G[1][2] * z2);
 #pragma unroll
@@ -334,7 +222,7 @@ __global__ __launch_bounds__(kCovThreads) void k_marg_grad(MargSchurParams p) {
   if (tid < 6) {
     double v = s_red[0][tid];
 #pragma unroll
-    for (int w = 1; w < kCovWaves; ++w) v += s_red[w][tid];
+    for (int w = 1; w < kElimWaves; ++w) v += s_red[w][tid];
     p.r[6 * a + tid] = v;
   }
 }
@@ -371,7 +259,7 @@ __global__ __launch_bounds__(kMargElimThreads) void k_marg_eliminate(MargElimina
   if (tid == 0) {
     int bad = -1;
     for (int i = 0; i < nd && bad < 0; ++i)
-      if (!cov_pivot_ok(p.S[(size_t)row_d(i) * n + row_d(i)])) bad = i;      // the FIRST bad diagonal entry
+      if (!elim_pivot_ok(p.S[(size_t)row_d(i) * n + row_d(i)])) bad = i;      // the FIRST bad diagonal entry
     s_bad = bad;
   }
   __syncthreads();
@@ -391,7 +279,7 @@ __global__ __launch_bounds__(kMargElimThreads) void k_marg_eliminate(MargElimina
   double piv = 1.0;
   for (int j = 0; j < nd; ++j) {
     const double d = A[(size_t)j * ld + j];
-    if (!cov_pivot_ok(d)) {
+    if (!elim_pivot_ok(d)) {
       if (tid == 0) { p.info[0] = piv; p.info[1] = (double)j; p.info[2] = 0.0; }
       return;
     }

@@ -66,10 +66,20 @@ class Engine:
     def __exit__(self, *a):
         self.close()
 
-    def _check(self, rc, what):
+    def _check(self, rc, what, **attrs):
+        """Raises EngineError for a status other than PBA_OK; `attrs` become attributes of the error."""
         if rc != 0:
-            raise EngineError("%s: %s (%s)" % (what, self._L.pba_status_string(rc).decode(),
+            err = EngineError("%s: %s (%s)" % (what, self._L.pba_status_string(rc).decode(),
                                                self._L.pba_last_error(self._h).decode()))
+            for k, v in attrs.items():
+                setattr(err, k, v)
+            raise err
+
+    def _check_info(self, rc, what, info, **extras):
+        """_check for a call with an info struct: returns its fields; the EngineError of a failure carries `status`, `info` and extras."""
+        fields = {f: getattr(info, f) for f, _ in info._fields_}
+        self._check(rc, what, status=rc, info=fields, **extras)
+        return fields
 
     # ---- data ------------------------------------------------------------------------------------------
     def set_frame(self, slot, image_u8):
@@ -310,11 +320,7 @@ class Engine:
         cam = np.zeros(n_max * n_max) if cameras else None
         pts = np.zeros((self.n_points, 3, 3)) if points else None
         rc = self._L.pba_covariance(self._h, _ptr(cam) if cameras else None, _ptr(pts) if points else None, C.byref(info))
-        fields = {f: getattr(info, f) for f, _ in _lib.CovarianceInfo._fields_}
-        if rc != 0:
-            err = EngineError("pba_covariance: %s (%s)" % (self._L.pba_status_string(rc).decode(), self._L.pba_last_error(self._h).decode()))
-            err.status, err.info = rc, fields
-            raise err
+        fields = self._check_info(rc, "pba_covariance", info)
         n = info.n_cam
         out = dict(fields)
         out["cam_cov"] = cam[:n * n].reshape(n, n).copy() if cameras else None
@@ -353,11 +359,7 @@ class Engine:
         eta = np.zeros(n_max)
         c = C.c_double(0.0)
         rc = self._L.pba_marginalize(self._h, mask, _ptr(slots), _ptr(x0), _ptr(Lm), _ptr(eta), C.byref(c), C.byref(info))
-        fields = {f: getattr(info, f) for f, _ in _lib.MarginalInfo._fields_}
-        if rc != 0:
-            err = EngineError("pba_marginalize: %s (%s)" % (self._L.pba_status_string(rc).decode(), self._L.pba_last_error(self._h).decode()))
-            err.status, err.info = rc, fields
-            raise err
+        fields = self._check_info(rc, "pba_marginalize", info)
         k = info.k
         out = dict(fields)
         out.update(slots=slots[:k].copy(), x0=x0[:k].copy(), Lambda=Lm[:36 * k * k].reshape(6 * k, 6 * k).copy(), eta=eta[:6 * k].copy(), c=c.value)
@@ -380,11 +382,7 @@ class Engine:
         keep = np.zeros(self.n_obs, np.uint8)
         pmap = np.zeros(self.n_points, np.int32)
         rc = self._L.pba_cull(self._h, C.byref(o), _ptr(keep), _ptr(pmap), C.byref(info))
-        fields = {f: getattr(info, f) for f, _ in _lib.CullInfo._fields_}
-        if rc != 0:
-            err = EngineError("pba_cull: %s (%s)" % (self._L.pba_status_string(rc).decode(), self._L.pba_last_error(self._h).decode()))
-            err.status, err.info, err.block_keep, err.point_map = rc, fields, keep, pmap
-            raise err
+        fields = self._check_info(rc, "pba_cull", info, block_keep=keep, point_map=pmap)
         if info.applied:
             self.n_points, self.n_obs = info.n_points_after, info.n_blocks_after
         return keep, pmap, fields

@@ -24,7 +24,7 @@ from photobundle_amd.engine import Engine, EngineError, default_solver_options  
 
 KITTI = dict(size=(376, 1241), K=(718.856, 718.856, 607.1928, 185.2157))
 N_IT = 20
-KERNELS = ("k_cov_point", "k_cov_schur", "k_cov_invert", "k_cov_points")
+KERNELS = ("k_cov_point", "k_elim_pair", "k_cov_invert", "k_cov_points")
 
 
 def make(shape):

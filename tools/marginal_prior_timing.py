@@ -33,7 +33,7 @@ from photobundle_amd.engine import Engine, default_solver_options  # noqa: E402
 
 KITTI = dict(size=(376, 1241), K=(718.856, 718.856, 607.1928, 185.2157))
 N_IT = 20
-KERNELS = ("k_marg_point", "k_marg_schur", "k_marg_grad", "k_prior", "k_marg_eliminate")
+KERNELS = ("k_marg_point", "k_elim_pair", "k_marg_grad", "k_prior", "k_marg_eliminate")
 ANCHORS, DROP = (0,), (0,)
 
 
