@@ -473,6 +473,66 @@ int pba_cull(pba_engine* e, const pba_cull_options* o,
              int32_t* point_map  /* [n_points before]: new index or -1, nullable */,
              pba_cull_info* info /* nullable */);
 
+/* ---- re-observation: the residual blocks the window should have, found once the solve has made the poses good -----------------
+ * A residual block enters through addFrame's one ZNCC test under the INITIAL pose (photobundle.cc:512-542); pba_admit looks at the pairs
+ * that test lost, at the refined state.  It is the counterpart of pba_cull: that call only ever shortens tracks, this one lengthens them.
+ * Candidates.  A candidate is a pair (p, s) that passes every one of these tests:
+ *     p is a point of the problem;
+ *     s is a bit of slot_mask;
+ *     (p, s) is NOT in the observation list;
+ *     at the current (best) state, the one pba_get_state returns, X_c = R_s X_p + t_s has z >= min_depth;
+ *     u = fx x / z + cx and v = fy y / z + cy satisfy border <= u <= cols - 1 - border and border <= v <= rows - 1 - border (as doubles).
+ * Every comparison fails on a non-finite value.  In the inverse-depth mode X_p = origin + direction / rho.
+ * Candidates are ordered by point ascending, then slot ascending: the order of the cand_* arrays.
+ * With border smaller than the patch radius the patch may cross the image edge: legal, the sampler's clamped taps serve it as they serve
+ * any such block.
+ * Candidate cost.  c = rho(|r|^2) / 2 of the residual block (p, s) at the current state: the engine's sampler, the patch weights, every
+ * channel, the engine's Huber threshold -- the number pba_get_block_costs would report for the block, computed by the kernel that computes
+ * those (the candidate list is handed to the Jacobian pass as an observation list of its own).
+ * The verdict, with n blocks in the problem:
+ *     k and quantile_cost as in pba_cull, over the costs of the blocks ALREADY in the problem (not the candidates);
+ *     threshold = factor > 0 ? fmax(min_cost, factor * quantile_cost) : min_cost;
+ *     candidate i is taken iff c_i <= threshold (a non-finite cost never is).
+ * cand_point, cand_slot, cand_cost, cand_take [capacity], each nullable: the first n_written = min(n_candidates, capacity) candidates; the
+ * counts in info are the full ones whatever the capacity.  capacity = 0 with null pointers is a count.
+ * The call runs pba_linearize when the current point has no valid linearisation (counted exactly as pba_covariance counts it) and moves
+ * nothing else of the LM state: the candidates are evaluated into buffers of the call's own, no record, cost or counter of the engine moves.
+ * apply == 0, or nothing taken: the engine is untouched (applied = 0; a following pba_solve gives the bits it would have given without the
+ * call).
+ * An applied admission (apply != 0, at least one candidate taken) leaves the engine as if pba_set_problem had been called with the merged
+ * lists -- per point the union of its old and its taken slots, ascending -- and the current parameters byte for byte (in the inverse-depth
+ * mode: rho and the rays) -- except that the cameras and the anchor mask, the camera prior, the inverse-depth mode and the points-constant /
+ * cameras-constant switches stay as they are.  The point set does not change: no row of the points, descriptors or rays moves.  The merged
+ * lists are written on the device into fresh buffers that are swapped in; the candidate list and the take bytes travel to the host, which
+ * rebuilds the tile tables.  The linearisation is dropped as pba_set_problem drops it: pba_step wants a pba_linearize first.  A free camera
+ * that had no residual block may gain some and become a live column.
+ * Every count is an integer sum and the order statistic an exact radix select: two fresh engines give the same bytes.
+ * Narrow and wide windows, any anchor mask, inverse depth, both constant modes, an engine holding a prior, engines of pba_solve_batch; every
+ * channel count and patch radius, unit and Gaussian weights.
+ * PBA_ERR_INVALID with a message in pba_last_error, before any launch, the engine unchanged: options outside their ranges; slot_mask zero,
+ * with a bit at or above n_frames, or on a slot without a frame; capacity < 0; multi-rank engines; the precision-sweep flags.
+ * PBA_ERR_NUMERIC: factor * quantile_cost is not finite (engine unchanged, nothing written to the cand_* arrays; info holds the counts
+ * before, n_candidates, quantile_cost and the non-finite product as threshold).  PBA_ERR_STATE as pba_linearize gives it. */
+typedef struct pba_admit_options {
+  uint32_t slot_mask;        /* slots that may gain blocks; non-zero, bits < n_frames, each holding a frame */
+  double   min_depth;        /* > 0, finite: z of the point in the camera must be >= this */
+  int32_t  border;           /* >= 0; the projection must satisfy border <= u <= cols-1-border, border <= v <= rows-1-border (doubles) */
+  double   min_cost, factor, quantile;   /* the threshold, exactly pba_cull's form and ranges */
+  int32_t  apply;            /* 0: verdict only */
+} pba_admit_options;
+
+typedef struct pba_admit_info {
+  int32_t n_blocks_before, n_blocks_after, n_points;
+  int32_t n_candidates, n_admitted;
+  int32_t n_written;         /* entries written to the cand_* arrays = min(n_candidates, capacity) */
+  double  quantile_cost, threshold;
+  int32_t applied;           /* 1 when the engine's observation lists were replaced */
+} pba_admit_info;
+
+int pba_admit(pba_engine* e, const pba_admit_options* o, int32_t capacity,
+              int32_t* cand_point, int32_t* cand_slot, double* cand_cost, uint8_t* cand_take,  /* [capacity], each nullable */
+              pba_admit_info* info /* nullable */);
+
 /* ---- several independent windows on one device ------------------------------------------------------------ */
 #define PBA_MAX_BATCH 64
 /* Solves n independent windows together: one launch of each phase of a pipelined LM iteration serves every window still running.

@@ -83,13 +83,16 @@ static Calibration loadCalibration(const std::string& fn) {
 
 // prior: the sequence runs with marginalize = 1 (one more line, the E of the prior the optimisation carried)
 // culled: the sequence runs with outlierPasses > 0 (one more line, the residual blocks and points the optimisation's culls removed)
-static void dumpResult(const std::string& fn, int frame, const PhotometricBundleAdjustment::Result& r, bool prior = false, bool culled = false) {
+// admitted: the sequence runs with reobservePasses > 0 (one more line, the residual blocks the optimisation's admissions added)
+static void dumpResult(const std::string& fn, int frame, const PhotometricBundleAdjustment::Result& r, bool prior = false, bool culled = false,
+                       bool admitted = false) {
   std::FILE* f = std::fopen(fn.c_str(), "a");
   if (!f) throw std::runtime_error("cannot open " + fn);
   std::fprintf(f, "result frame %d poses %zu points %zu iterations %zu\n", frame, r.poses.size(), r.refinedPoints.size(), r.iterationSummary.size());
   std::fprintf(f, "cost %.17g %.17g %.17g steps %d residuals %d\n", r.initialCost, r.finalCost, r.fixedCost, r.numSuccessfulStep, r.numResiduals);
   if (prior) std::fprintf(f, "prior %.17g\n", r.priorCost);
   if (culled) std::fprintf(f, "culled blocks %d points %d\n", r.numCulledBlocks, r.numCulledPoints);
+  if (admitted) std::fprintf(f, "admitted blocks %d\n", r.numAdmittedBlocks);
   std::fprintf(f, "message %s\n", r.message.c_str());
   for (const auto& it : r.iterationSummary)
     std::fprintf(f, "it %d %d %d %.17g %.17g %.17g %.17g %.17g %.17g\n", it.iteration, (int)it.step_is_valid, (int)it.step_is_successful, it.cost,
@@ -270,6 +273,7 @@ int main(int argc, char** argv) {
     const int outlier_passes = PhotometricBundleAdjustment::Options(*q.cf).outlierPasses;
     TrackOptions track_options;
     track_options.outlierPasses = outlier_passes;
+    const int reobserve_passes = PhotometricBundleAdjustment::Options(*q.cf).reobservePasses;
     Mat44 T_last = Mat44::Identity();      // (InitialPose = track) the frame-to-frame pose the previous frame was added with
     for (int f_i = 0; (q.track || f_i < (int)q.T_init.size()) && !gStop; ++f_i) {
       if (!q.read(f_i)) break;
@@ -296,7 +300,7 @@ int main(int argc, char** argv) {
       result.initialCost = -1.0;    // the class only touches `result` when an optimisation ran (photobundle.cc:857)
       if (photoba_pyr) photoba_pyr->addFrame(q.img.data(), q.depth.data(), T, &result);
       else photoba->addFrame(q.img.data(), q.depth.data(), T, &result);
-      if (!results.empty() && result.initialCost >= 0.0) dumpResult(results, f_i, result, with_prior, outlier_passes > 0);
+      if (!results.empty() && result.initialCost >= 0.0) dumpResult(results, f_i, result, with_prior, outlier_passes > 0, reobserve_passes > 0);
     }
     writePoses(output, result, full_precision);
   } catch (const std::exception& ex) {

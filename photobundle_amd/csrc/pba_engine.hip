@@ -18,6 +18,7 @@
 #include "pba_cov.h"
 #include "pba_prior.h"
 #include "pba_cull.h"
+#include "pba_admit.h"
 
 #include <algorithm>
 #include <chrono>
@@ -244,6 +245,25 @@ struct pba_engine : pba::Handle {      // (device, stream, err, mem, events)
   double* d_cull_rays = nullptr;
   int32_t* d_cull_obs_point = nullptr;
   uint8_t* d_cull_obs_slot = nullptr;
+
+  // re-observation (pba_admit, pba_admit.h): everything on first use, nothing shared with the LM or with pba_cull
+  uint32_t* d_admit_hist = nullptr;       // [kCullPasses][kCullBins] radix-select tables
+  uint64_t* d_admit_sel = nullptr;        // [kCullSelWords]
+  uint32_t* d_admit_cand_mask = nullptr;  // [n_points] candidate slots
+  uint32_t* d_admit_take_mask = nullptr;  // [n_points] taken slots
+  int32_t* d_admit_cand_begin = nullptr;  // [n_points]
+  uint2* d_admit_part = nullptr;          // [point blocks] workgroup sums
+  uint2* d_admit_off = nullptr;           // [point blocks] their exclusive scan
+  int32_t* d_admit_tot = nullptr;         // [kAdmitTotals]
+  int32_t* d_admit_cand_point = nullptr;  // [n_cand] the candidate list: an observation list of its own
+  uint8_t* d_admit_cand_slot = nullptr;
+  uint8_t* d_admit_cand_take = nullptr;
+  double* d_admit_rec = nullptr;          // [6][stride] the candidates' records (row 5: their costs)
+  double* d_admit_block_cost = nullptr;   // [workgroups of the candidates' pass]
+  int32_t* d_admit_block_fail = nullptr;
+  int32_t* d_admit_obs_point = nullptr;   // the fresh buffers the merged lists are written into; an applied admission exchanges them with
+  uint8_t* d_admit_obs_slot = nullptr;    // d_obs_point, d_obs_slot
+  int32_t* d_admit_pt_begin = nullptr;    // [n_points + 1] of the merged list
 
   // batched solves (pba_solve_batch, pba_batch.h): the window table lives with the batch's FIRST engine (grow-only), whose stream
   // carries the batch; while a batch runs every engine's `stream` names that stream and `stream_own` keeps its own
@@ -2414,6 +2434,175 @@ int pba_cull(pba_engine* e, const pba_cull_options* o, uint8_t* block_keep, int3
   e->mem.exchange(&e->d_obs_point, &e->d_cull_obs_point);
   e->mem.exchange(&e->d_obs_slot, &e->d_cull_obs_slot);
   if (e->inverse_depth) e->mem.exchange(&e->d_rays, &e->d_cull_rays);
+  if ((rc = problem_reserve(e, L, PD))) return rc;
+  if ((rc = problem_upload_tables(e, L))) return rc;
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  problem_installed(e, &L);
+  invalidate(e, kInProblem);
+  inf.applied = 1;
+  if (info) *info = inf;
+  return PBA_OK;
+}
+
+// ---- re-observation (pba_admit.h) -------------------------------------------------------------------------------------------------
+// The Jacobian pass of the current state over ANOTHER observation list of the same points: the kernel, the sampler and the loss of
+// pba_linearize, records and block partials into the caller's buffers.  No counter, event or validity flag of the engine moves.
+static void admit_sample_list(pba_engine* e, SampleParams sp, int n) {
+  const int grid = e->sample_grid;
+  e->sample_grid = (n + e->sample_waves * 64 - 1) / (e->sample_waves * 64);
+  launch_sample<true>(e, sp);
+  e->sample_grid = grid;
+}
+
+// Sizing: count, then fill.  k_admit_enum + k_admit_offsets give the number of candidates, the host reads it (one int) and sizes the list,
+// the records and the launch of the candidates' pass by it; the same pair (k_admit_count + k_admit_offsets) sizes the merged lists.
+int pba_admit(pba_engine* e, const pba_admit_options* o, int32_t capacity, int32_t* cand_point, int32_t* cand_slot, double* cand_cost, uint8_t* cand_take,
+              pba_admit_info* info) {
+  if (!e || !o) return PBA_ERR_INVALID;
+  pba_admit_info inf{};
+  if (info) *info = inf;
+  if (!(o->min_depth > 0.0) || !std::isfinite(o->min_depth)) return fail(e, PBA_ERR_INVALID, "pba_admit: min_depth = %g must be finite and > 0", o->min_depth);
+  if (o->border < 0) return fail(e, PBA_ERR_INVALID, "pba_admit: border = %d must be >= 0", o->border);
+  if (!(o->min_cost >= 0.0) || !std::isfinite(o->min_cost)) return fail(e, PBA_ERR_INVALID, "pba_admit: min_cost = %g must be finite and >= 0", o->min_cost);
+  if (!(o->factor >= 0.0) || !std::isfinite(o->factor)) return fail(e, PBA_ERR_INVALID, "pba_admit: factor = %g must be finite and >= 0", o->factor);
+  if (!(o->quantile >= 0.0 && o->quantile <= 1.0)) return fail(e, PBA_ERR_INVALID, "pba_admit: quantile = %g must be in [0, 1]", o->quantile);
+  if (capacity < 0) return fail(e, PBA_ERR_INVALID, "pba_admit: capacity = %d must be >= 0", capacity);
+  if (o->slot_mask == 0) return fail(e, PBA_ERR_INVALID, "pba_admit: slot_mask is empty");
+  if (const char* why = mode_conflict(modes_present(e, e->comm.multi()), kModeAdmit)) return fail(e, PBA_ERR_INVALID, "pba_admit: %s", why);
+  { const int rc0 = check_ready(e, "pba_admit"); if (rc0) return rc0; }
+  if (e->n_frames < 32 && (o->slot_mask >> e->n_frames))
+    return fail(e, PBA_ERR_INVALID, "pba_admit: slot_mask 0x%x has bits at or above n_frames = %d", o->slot_mask, e->n_frames);
+  for (int s = 0; s < e->n_frames; ++s)
+    if (((o->slot_mask >> s) & 1u) && !e->frame_set[s]) return fail(e, PBA_ERR_INVALID, "pba_admit: slot %d of slot_mask holds no frame", s);
+  PBA_ENTER(e);
+  int rc;
+  if ((rc = pba_linearize(e, nullptr))) return rc;
+  const int n_obs = e->n_obs, n_points = e->n_points, cur = e->cur;
+  const int pt_blocks = (n_points + kAdmitThreads - 1) / kAdmitThreads;
+  if ((rc = dev_alloc(e, &e->d_admit_hist, (size_t)kCullPasses * kCullBins))) return rc;
+  if ((rc = dev_alloc(e, &e->d_admit_sel, (size_t)kCullSelWords))) return rc;
+  if ((rc = dev_alloc(e, &e->d_admit_cand_mask, (size_t)n_points))) return rc;
+  if ((rc = dev_alloc(e, &e->d_admit_take_mask, (size_t)n_points))) return rc;
+  if ((rc = dev_alloc(e, &e->d_admit_cand_begin, (size_t)n_points))) return rc;
+  if ((rc = dev_alloc(e, &e->d_admit_part, (size_t)pt_blocks))) return rc;
+  if ((rc = dev_alloc(e, &e->d_admit_off, (size_t)pt_blocks))) return rc;
+  if ((rc = dev_alloc(e, &e->d_admit_tot, (size_t)kAdmitTotals))) return rc;
+
+  AdmitParams ap{};
+  ap.xyz = e->d_xyz[cur]; ap.rays = rays_or_null(e); ap.geom = e->d_geom[cur]; ap.pt_begin = e->d_pt_begin; ap.obs_slot = e->d_obs_slot;
+  ap.sel = e->d_admit_sel; ap.cand_mask = e->d_admit_cand_mask; ap.take_mask = e->d_admit_take_mask; ap.cand_begin = e->d_admit_cand_begin;
+  ap.part = e->d_admit_part; ap.off = e->d_admit_off; ap.tot = e->d_admit_tot;
+  ap.fx = e->cfg.fx; ap.fy = e->cfg.fy; ap.cx = e->cfg.cx; ap.cy = e->cfg.cy;
+  ap.min_depth = o->min_depth;
+  ap.u_lo = (double)o->border; ap.u_hi = (double)(e->cfg.cols - 1 - o->border);
+  ap.v_lo = (double)o->border; ap.v_hi = (double)(e->cfg.rows - 1 - o->border);
+  ap.slot_mask = o->slot_mask; ap.n_points = n_points; ap.n_frames = e->n_frames; ap.n_part = pt_blocks;
+
+  // the count ...
+  int32_t tot[kAdmitTotals] = {0, 0};
+  hipLaunchKernelGGL(k_admit_enum, dim3(pt_blocks), dim3(kAdmitThreads), 0, e->stream, ap);
+  hipLaunchKernelGGL(k_admit_offsets, dim3(1), dim3(kAdmitThreads), 0, e->stream, ap);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipMemcpyAsync(tot, e->d_admit_tot, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  const int n_cand = tot[0];
+  const int cand_blocks = (n_cand + kAdmitThreads - 1) / kAdmitThreads;
+  ap.n_cand = n_cand;
+
+  // ... then the fill, and the candidates' costs through the Jacobian pass
+  const int64_t cand_stride = ((int64_t)n_cand + 255) / 256 * 256;
+  if (n_cand > 0) {
+    const int sample_blocks = (n_cand + e->sample_waves * 64 - 1) / (e->sample_waves * 64);
+    if ((rc = dev_alloc(e, &e->d_admit_cand_point, (size_t)n_cand))) return rc;
+    if ((rc = dev_alloc(e, &e->d_admit_cand_slot, (size_t)n_cand))) return rc;
+    if ((rc = dev_alloc(e, &e->d_admit_cand_take, (size_t)n_cand))) return rc;
+    if ((rc = dev_alloc(e, &e->d_admit_rec, (size_t)6 * cand_stride))) return rc;
+    if ((rc = dev_alloc(e, &e->d_admit_block_cost, (size_t)sample_blocks))) return rc;
+    if ((rc = dev_alloc(e, &e->d_admit_block_fail, (size_t)sample_blocks))) return rc;
+    ap.cand_point = e->d_admit_cand_point; ap.cand_slot = e->d_admit_cand_slot; ap.cand_take = e->d_admit_cand_take;
+    ap.cand_cost = e->d_admit_rec + 5 * cand_stride;
+    hipLaunchKernelGGL(k_admit_fill, dim3(pt_blocks), dim3(kAdmitThreads), 0, e->stream, ap);
+    SampleParams sp = make_sample_params(e, cur);
+    sp.obs_point = e->d_admit_cand_point; sp.obs_slot = e->d_admit_cand_slot; sp.n_obs = n_cand;
+    sp.rec = e->d_admit_rec; sp.rec_stride = cand_stride; sp.block_cost = e->d_admit_block_cost; sp.block_fail = e->d_admit_block_fail;
+    admit_sample_list(e, sp, n_cand);
+  }
+
+  // the verdict: the order statistic over the costs of the problem's own blocks, the threshold, one lane per candidate
+  const int64_t k = (int64_t)std::floor(o->quantile * (double)(n_obs - 1));
+  const double* cost = e->d_rec[cur] + 5 * e->rec_stride;
+  cull_enqueue_select(e->stream, reinterpret_cast<const uint64_t*>(cost), n_obs, (uint32_t)k, e->d_admit_hist, e->d_admit_sel, 1, o->min_cost, o->factor);
+  HIP_TRY(e, hipMemsetAsync(e->d_admit_take_mask, 0, sizeof(uint32_t) * n_points, e->stream));
+  if (n_cand > 0) hipLaunchKernelGGL(k_admit_verdict, dim3(cand_blocks), dim3(kAdmitThreads), 0, e->stream, ap);
+  hipLaunchKernelGGL(k_admit_count, dim3(pt_blocks), dim3(kAdmitThreads), 0, e->stream, ap);
+  hipLaunchKernelGGL(k_admit_offsets, dim3(1), dim3(kAdmitThreads), 0, e->stream, ap);
+  HIP_TRY(e, hipGetLastError());
+  uint64_t sel[kCullSelWords] = {0, 0, 0};
+  std::vector<int32_t> h_point(n_cand);
+  std::vector<uint8_t> h_slot(n_cand), h_take(n_cand);
+  std::vector<double> h_cost(n_cand);
+  HIP_TRY(e, hipMemcpyAsync(sel, e->d_admit_sel, sizeof(sel), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(tot, e->d_admit_tot, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
+  if (n_cand > 0) {
+    HIP_TRY(e, hipMemcpyAsync(h_point.data(), e->d_admit_cand_point, sizeof(int32_t) * n_cand, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(h_slot.data(), e->d_admit_cand_slot, (size_t)n_cand, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(h_take.data(), e->d_admit_cand_take, (size_t)n_cand, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(h_cost.data(), ap.cand_cost, sizeof(double) * n_cand, hipMemcpyDeviceToHost, e->stream));
+  }
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+
+  inf.n_blocks_before = inf.n_blocks_after = n_obs;
+  inf.n_points = n_points;
+  inf.n_candidates = n_cand;
+  std::memcpy(&inf.quantile_cost, &sel[0], sizeof(double));
+  std::memcpy(&inf.threshold, &sel[1], sizeof(double));
+  if (sel[2]) {
+    if (info) *info = inf;
+    return fail(e, PBA_ERR_NUMERIC, "pba_admit: factor * quantile_cost = %g * %g is not finite", o->factor, inf.quantile_cost);
+  }
+  inf.n_blocks_after = tot[0]; inf.n_admitted = tot[1];
+  inf.n_written = std::min(n_cand, capacity);
+  for (int i = 0; i < inf.n_written; ++i) {
+    if (cand_point) cand_point[i] = h_point[i];
+    if (cand_slot) cand_slot[i] = h_slot[i];
+    if (cand_cost) cand_cost[i] = h_cost[i];
+    if (cand_take) cand_take[i] = h_take[i];
+  }
+  if (info) *info = inf;
+  if (!o->apply || inf.n_admitted == 0) return PBA_OK;
+  if (inf.n_blocks_after != n_obs + inf.n_admitted) return fail(e, PBA_ERR_HIP, "pba_admit: the merged count %d is not %d + %d", inf.n_blocks_after, n_obs, inf.n_admitted);
+
+  // the merged lists, written into fresh buffers that then take the place of the engine's
+  const int n_after = inf.n_blocks_after;
+  if ((rc = dev_alloc(e, &e->d_admit_obs_point, (size_t)n_after))) return rc;
+  if ((rc = dev_alloc(e, &e->d_admit_obs_slot, (size_t)n_after))) return rc;
+  if ((rc = dev_alloc(e, &e->d_admit_pt_begin, (size_t)n_points + 1))) return rc;
+  ap.obs_point_new = e->d_admit_obs_point; ap.obs_slot_new = e->d_admit_obs_slot; ap.pt_begin_new = e->d_admit_pt_begin;
+  hipLaunchKernelGGL(k_admit_merge, dim3(pt_blocks), dim3(kAdmitThreads), 0, e->stream, ap, (int32_t)n_after);
+  HIP_TRY(e, hipGetLastError());
+  // ... and on the host, from the candidate list and the take bytes, for the tile builder pba_set_problem runs
+  std::vector<int32_t> op((size_t)n_after), os((size_t)n_after);
+  {
+    size_t d = 0, c = 0;
+    for (int p = 0; p < n_points; ++p) {
+      int ob = e->h_pt_begin[p];
+      const int ob1 = e->h_pt_begin[p + 1];
+      while (c < (size_t)n_cand && h_point[c] == p && !h_take[c]) ++c;
+      while (ob < ob1 || (c < (size_t)n_cand && h_point[c] == p)) {
+        const bool have_new = c < (size_t)n_cand && h_point[c] == p;
+        if (ob < ob1 && (!have_new || e->h_obs_slot[ob] < h_slot[c])) { op[d] = p; os[d] = e->h_obs_slot[ob]; ++ob; }
+        else { op[d] = p; os[d] = h_slot[c]; ++c; while (c < (size_t)n_cand && h_point[c] == p && !h_take[c]) ++c; }
+        ++d;
+      }
+    }
+    if (d != (size_t)n_after) return fail(e, PBA_ERR_HIP, "pba_admit: the host's merged list holds %zu blocks, the device's %d", d, n_after);
+  }
+  HIP_TRY(e, hipStreamSynchronize(e->stream));      // (the merge read d_pt_begin / d_obs_slot: done before they are replaced)
+  const int PD = pba_internal_patch_len(e);
+  ProblemLayout L;
+  if ((rc = problem_layout(e, n_points, n_after, op.data(), os.data(), &L))) return rc;
+  e->mem.exchange(&e->d_obs_point, &e->d_admit_obs_point);
+  e->mem.exchange(&e->d_obs_slot, &e->d_admit_obs_slot);
   if ((rc = problem_reserve(e, L, PD))) return rc;
   if ((rc = problem_upload_tables(e, L))) return rc;
   HIP_TRY(e, hipStreamSynchronize(e->stream));

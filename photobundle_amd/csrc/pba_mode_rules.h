@@ -12,7 +12,8 @@ namespace pba {
 enum ModeFeature : unsigned {      // one bit each
   kModeMulti = 1, kModeInverseDepth = 2, kModeSweep = 4 /* pba_config.flags bits 1-2 */, kModeWide = 8, kModePointsConst = 16, kModeCamsConst = 32,
   kModeAnchors = 64 /* two or more constant slots */, kModeCovariance = 128 /* pba_covariance */, kModeBatch = 256 /* pba_solve_batch */,
-  kModePrior = 512 /* pba_set_camera_prior; pba_marginalize asks as if it switched one on */, kModeCull = 1024 /* pba_cull */
+  kModePrior = 512 /* pba_set_camera_prior; pba_marginalize asks as if it switched one on */, kModeCull = 1024 /* pba_cull */,
+  kModeAdmit = 2048 /* pba_admit */
 };
 struct ModeRule { unsigned a, b; const char* then_b; const char* then_a; };
 constexpr ModeRule kModeRules[] = {
@@ -50,6 +51,8 @@ constexpr ModeRule kModeRules[] = {
     {kModePrior, kModeBatch, "the camera prior (pba_set_camera_prior) solves alone", nullptr},
     {kModeMulti, kModeCull, "multi-rank engines (pba_comm_*) are not built for culling: the order statistic would need an exchange", nullptr},
     {kModeSweep, kModeCull, "the precision-sweep sampler modes (pba_config.flags bits 1-2) are not built for culling", nullptr},
+    {kModeMulti, kModeAdmit, "multi-rank engines (pba_comm_*) are not built for re-observation: the order statistic would need an exchange", nullptr},
+    {kModeSweep, kModeAdmit, "the precision-sweep sampler modes (pba_config.flags bits 1-2) are not built for re-observation", nullptr},
 };
 
 // Why feature `on` (one bit) cannot be switched on next to the features `present` (nullptr: it can); *with: the feature in its way

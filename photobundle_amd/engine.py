@@ -387,6 +387,31 @@ class Engine:
             self.n_points, self.n_obs = info.n_points_after, info.n_blocks_after
         return keep, pmap, fields
 
+    # ---- re-observation ----------------------------------------------------------------------------------------
+    def admit(self, slot_mask=None, min_depth=0.1, border=None, min_cost=0.0, factor=1.0, quantile=0.5, apply=True, capacity=None):
+        """pba_admit: the (point, slot) pairs missing from the observation list whose projection at the current state lies inside the
+        image, the verdict over their block costs and, with apply, the engine's lists merged with the ones taken (include/pba.h).
+        slot_mask None: every slot below n_frames; border None: the patch radius; capacity None: room for every candidate.
+        Returns (cand_point int32, cand_slot int32, cand_cost float64, cand_take uint8, info dict), the arrays n_written long; n_obs
+        follows an applied admission.  Raises EngineError otherwise; its `status` and `info` attributes carry the status code and the
+        info fields."""
+        if slot_mask is None:
+            slot_mask = (1 << self.n_frames) - 1
+        slot_mask = int(slot_mask) & 0xFFFFFFFF
+        if border is None:
+            border = self.cfg.radius
+        o = _lib.AdmitOptions(slot_mask, float(min_depth), int(border), float(min_cost), float(factor), float(quantile), 1 if apply else 0)
+        info = _lib.AdmitInfo()
+        # (no call reports more candidates than there are (point, slot) pairs; a capacity <= 0 goes with null pointers)
+        cap = self.n_points * bin(slot_mask).count("1") if capacity is None else int(capacity)
+        room = max(cap, 0)
+        out = np.zeros(room, np.int32), np.zeros(room, np.int32), np.zeros(room), np.zeros(room, np.uint8)
+        rc = self._L.pba_admit(self._h, C.byref(o), cap, *[_ptr(a) if room else None for a in out], C.byref(info))
+        fields = self._check_info(rc, "pba_admit", info)
+        if info.applied:
+            self.n_obs = info.n_blocks_after
+        return tuple(a[:info.n_written].copy() for a in out) + (fields,)
+
     def select_u64order(self, v, k):
         """Test hook (pba_internal_select_u64order): the k-th smallest of v by 64-bit pattern, through the select kernels of pba_cull."""
         v = np.ascontiguousarray(v, np.float64).ravel()

@@ -20,6 +20,7 @@
 #include <unordered_map>
 
 #include "../../include/pba.h"
+#include "admit_lists.h"
 #include "imgproc.h"
 #include "utils.h"
 
@@ -178,7 +179,11 @@ PhotometricBundleAdjustment::Options::Options(const utils::ConfigFile& cf)
       outlierQuantile(cf.get<double>("outlierQuantile", 0.5)),
       outlierFactor(cf.get<double>("outlierFactor", 3.0)),
       outlierMinCost(cf.get<double>("outlierMinCost", 0.0)),
-      outlierMinObservations(cf.get<int>("outlierMinObservations", 2)) {}
+      outlierMinObservations(cf.get<int>("outlierMinObservations", 2)),
+      reobservePasses(cf.get<int>("reobservePasses", 0)),
+      reobserveFactor(cf.get<double>("reobserveFactor", 1.0)),
+      reobserveQuantile(cf.get<double>("reobserveQuantile", 0.5)),
+      reobserveMinCost(cf.get<double>("reobserveMinCost", 0.0)) {}
 
 std::ostream& operator<<(std::ostream& os, const PhotometricBundleAdjustment::Options& o) {
   using DT = PhotometricBundleAdjustment::Options::DescriptorType;
@@ -191,7 +196,9 @@ std::ostream& operator<<(std::ostream& os, const PhotometricBundleAdjustment::Op
      << "\ncamerasConstant = " << (o.camerasConstant ? 1 : 0) << "\nnumConstantFrames = " << o.numConstantFrames
      << "\ncomputeCovariance = " << (o.computeCovariance ? 1 : 0) << "\nmarginalize = " << (o.marginalize ? 1 : 0)
      << "\noutlierPasses = " << o.outlierPasses << "\noutlierQuantile = " << o.outlierQuantile << "\noutlierFactor = " << o.outlierFactor
-     << "\noutlierMinCost = " << o.outlierMinCost << "\noutlierMinObservations = " << o.outlierMinObservations << "\n";
+     << "\noutlierMinCost = " << o.outlierMinCost << "\noutlierMinObservations = " << o.outlierMinObservations
+     << "\nreobservePasses = " << o.reobservePasses << "\nreobserveFactor = " << o.reobserveFactor << "\nreobserveQuantile = " << o.reobserveQuantile
+     << "\nreobserveMinCost = " << o.reobserveMinCost << "\n";
   return os;
 }
 
@@ -263,8 +270,9 @@ struct PhotometricBundleAdjustment::ScenePoint {
   bool was_refined = false;
   bool ref_culled = false;       // Options::outlierPasses: the block of the reference frame was culled (the frame stays in `f`)
   int x0 = 0, y0 = 0;
-  ScenePoint(const Vec3& X_, uint32_t f_id) : X(X_), X_original(X_) { f.reserve(8); f.push_back(f_id); }
-  uint32_t refFrameId() const { return f.front(); }
+  uint32_t ref_id;               // the frame the point was created in: f.front(), until Options::reobservePasses admits an EARLIER frame
+  ScenePoint(const Vec3& X_, uint32_t f_id) : X(X_), X_original(X_), ref_id(f_id) { f.reserve(8); f.push_back(f_id); }
+  uint32_t refFrameId() const { return ref_id; }
   uint32_t lastFrameId() const { return f.back(); }
   size_t numFrames() const { return f.size(); }
 };
@@ -297,6 +305,16 @@ PhotometricBundleAdjustment::PhotometricBundleAdjustment(const Calibration& cali
       throw std::invalid_argument("outlierMinCost = " + std::to_string(options.outlierMinCost) + " must be finite and >= 0");
     if (options.outlierMinObservations < 1)
       throw std::invalid_argument("outlierMinObservations = " + std::to_string(options.outlierMinObservations) + " is below 1: a point needs at least one residual block");
+  }
+  if (options.reobservePasses < 0)
+    throw std::invalid_argument("reobservePasses = " + std::to_string(options.reobservePasses) + " is negative: 0 switches the re-observation off");
+  if (options.reobservePasses > 0) {
+    if (!(options.reobserveQuantile >= 0.0 && options.reobserveQuantile <= 1.0))
+      throw std::invalid_argument("reobserveQuantile = " + std::to_string(options.reobserveQuantile) + " is outside 0 .. 1");
+    if (!(options.reobserveFactor >= 0.0) || !std::isfinite(options.reobserveFactor))
+      throw std::invalid_argument("reobserveFactor = " + std::to_string(options.reobserveFactor) + " must be finite and >= 0 (0: reobserveMinCost alone is the threshold)");
+    if (!(options.reobserveMinCost >= 0.0) || !std::isfinite(options.reobserveMinCost))
+      throw std::invalid_argument("reobserveMinCost = " + std::to_string(options.reobserveMinCost) + " must be finite and >= 0");
   }
   // Multi-channel descriptor types: the reference's debug builds stop at `assert(p0.size() == w.size())`
   // (photobundle.cc:684: C P descriptor entries against P patch weights); its release builds run, with the weights
@@ -694,6 +712,8 @@ struct PhotometricBundleAdjustment::OptimizeState {
   std::vector<ScenePoint*> selected;
   std::vector<int32_t> obs_point, obs_slot;      // the observation list the engine holds (Options::outlierPasses maps removed blocks back)
   int culled_blocks = 0, culled_points = 0;      // Options::outlierPasses, summed over the passes
+  int admitted_blocks = 0;                       // Options::reobservePasses, summed over the passes
+  std::vector<std::pair<const ScenePoint*, uint32_t>> admitted;      // ... and which: (scene point, frame id)
   pba_solver_options so;
   pba_solver_summary summary;
   std::vector<pba_iteration_summary> its;
@@ -711,10 +731,66 @@ void PhotometricBundleAdjustment::optimize(Result* result) {
   OptimizeState st;
   if (optimizeAssemble(st)) {
     check(_engine, pba_solve(_engine, &st.so, &st.summary, st.its.data(), (int32_t)st.its.size()), "pba_solve");
+    if (_options_ptr->reobservePasses > 0) admitAndResolve(st);      // first: a cull then judges the admitted blocks too
     if (_options_ptr->outlierPasses > 0) cullAndResolve(st);
     st.lap(3);
   }
   optimizeFinish(st, result);
+}
+
+// Options::reobservePasses: pba_admit, then pba_solve with the admitted blocks, until the passes are used up or a pass admits nothing.
+// The state follows the engine's problem: the observation list grows by the candidates taken, and every admitted block adds its frame
+// to its scene point's visibility list, in ascending order (a reference-frame block that a cull of an earlier window took out comes
+// back by losing its mark).  An admission the engine refuses (a non-finite threshold, minValidDepth <= 0) ends the passes and says so
+// on stderr; the solve that stands is the last one.
+void PhotometricBundleAdjustment::admitAndResolve(OptimizeState& st) {
+  const Options& op = *_options_ptr;
+  const uint32_t window = (uint32_t)op.slidingWindowSize;
+  const double first_initial_cost = st.summary.initial_cost;
+  pba_admit_options ao;
+  ao.slot_mask = 0;
+  for (uint32_t id = st.frame_id_start; id <= st.frame_id_end; ++id) ao.slot_mask |= 1u << (id % window);
+  ao.min_depth = op.minValidDepth;
+  ao.border = std::max(op.maskBlockRadius, std::max(2, op.patchRadius));      // addFrame's B
+  ao.min_cost = op.reobserveMinCost; ao.factor = op.reobserveFactor; ao.quantile = op.reobserveQuantile;
+  ao.apply = 1;
+  int n_slots = 0;
+  for (uint32_t m = ao.slot_mask; m; m &= m - 1) ++n_slots;
+  for (int pass = 0; pass < op.reobservePasses; ++pass) {
+    const size_t bound = st.selected.size() * (size_t)n_slots;      // every (point, slot) pair: no call can report more
+    if (bound > (size_t)INT32_MAX) break;
+    std::vector<int32_t> cand_point(bound), cand_slot(bound);
+    std::vector<uint8_t> cand_take(bound);
+    pba_admit_info info;
+    const int rc = pba_admit(_engine, &ao, (int32_t)bound, cand_point.data(), cand_slot.data(), nullptr, cand_take.data(), &info);
+    if (rc == PBA_ERR_INVALID || rc == PBA_ERR_NUMERIC) {
+      std::fprintf(stderr, "re-observation pass %d stopped: pba_admit: %s (%s)\n", pass, pba_status_string(rc), pba_last_error(_engine));
+      break;
+    }
+    check(_engine, rc, "pba_admit");
+    if (op.verbose)
+      std::fprintf(stderr, "re-observation pass %d: %d candidates, %d at or under the threshold %.6g, %d -> %d residual blocks\n", pass,
+                   info.n_candidates, info.n_admitted, info.threshold, info.n_blocks_before, info.n_blocks_after);
+    if (!info.applied) break;
+    for (int32_t c = 0; c < info.n_written; ++c) {
+      if (!cand_take[(size_t)c]) continue;
+      ScenePoint* pt = st.selected[(size_t)cand_point[(size_t)c]];
+      const uint32_t id = st.frame_id_start + ((uint32_t)cand_slot[(size_t)c] + window - st.frame_id_start % window) % window;
+      if (id == pt->refFrameId()) pt->ref_culled = false;
+      else admit_lists::InsertAscending(pt->f, id);
+      st.admitted.emplace_back(pt, id);
+    }
+    st.admitted_blocks += admit_lists::MergeTaken(st.obs_point, st.obs_slot, info.n_written, cand_point.data(), cand_slot.data(), cand_take.data());
+    check(_engine, pba_solve(_engine, &st.so, &st.summary, st.its.data(), (int32_t)st.its.size()), "pba_solve (re-observation pass)");
+  }
+  st.summary.initial_cost = first_initial_cost;
+}
+
+std::vector<std::vector<uint32_t>> PhotometricBundleAdjustment::visibilityLists() const {
+  std::vector<std::vector<uint32_t>> out;
+  out.reserve(_scene_points.size());
+  for (const auto& pt : _scene_points) out.push_back(pt->f);
+  return out;
 }
 
 // Options::outlierPasses: pba_cull, then pba_solve on the survivors, until the passes are used up or a cull removes nothing.  The state
@@ -987,6 +1063,16 @@ void PhotometricBundleAdjustment::optimizeFinish(OptimizeState& st, Result* resu
     result->numResiduals = summary.num_residuals;
     result->numCulledBlocks = st.culled_blocks;
     result->numCulledPoints = st.culled_points;
+    result->numAdmittedBlocks = st.admitted_blocks;
+    result->admittedBlocks.clear();
+    if (!st.admitted.empty()) {
+      std::unordered_map<const ScenePoint*, uint32_t> position;
+      for (size_t i = 0; i < _scene_points.size(); ++i) position[_scene_points[i].get()] = (uint32_t)i;
+      for (const auto& a : st.admitted) {
+        const auto it = position.find(a.first);
+        if (it != position.end()) result->admittedBlocks.emplace_back(it->second, a.second);
+      }
+    }
     result->message = summary.message;
     result->iterationSummary.clear();
     for (int i = 0; i < summary.num_iterations; ++i) {
@@ -1060,6 +1146,10 @@ void PhotometricBundleAdjustment::addFrames(const std::vector<PhotometricBundleA
     if (instances[i]->_options_ptr->outlierPasses > 0)
       throw std::invalid_argument("addFrames: Options::outlierPasses solves alone (a cull sits between two solves of one window, and batched culling is "
                                   "not built); use addFrame");
+  for (size_t i = 0; i < n; ++i)
+    if (instances[i]->_options_ptr->reobservePasses > 0)
+      throw std::invalid_argument("addFrames: Options::reobservePasses solves alone (an admission sits between two solves of one window, and batched "
+                                  "admission is not built); use addFrame");
   auto result_of = [&](size_t i) { return results.empty() ? nullptr : results[i]; };
   std::vector<size_t> due;
   for (size_t i = 0; i < n; ++i)

@@ -15,6 +15,7 @@
 #include <cstdint>
 #include <iosfwd>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "calibration.h"
@@ -106,6 +107,10 @@ class PhotometricBundleAdjustment {
   // fewer than minPoints points it returns T_init and tracked = false.
   Mat44 trackFrame(const uint8_t* image, const Mat44& T_init, const TrackOptions& options = TrackOptions(), TrackResult* result = nullptr);
 
+  // Diagnostics (new): the visibility list of every scene point the instance holds, in the order it holds them -- the ids of the frames
+  // whose residual blocks the point has, ascending.
+  std::vector<std::vector<uint32_t>> visibilityLists() const;
+
   // Several independent sequences in lockstep (new): addFrame's front-end for every instance, then ONE pba_solve_batch per kernel key
   // (patch radius, descriptor channels, Gaussian weighting) over every instance whose window is full, then each instance's read-back,
   // eviction and Result.  Each instance ends exactly where its own addFrame would.  frames[i] / results[i] (results may be empty or hold
@@ -168,6 +173,21 @@ class PhotometricBundleAdjustment {
     double outlierFactor = 3.0;
     double outlierMinCost = 0.0;
     int outlierMinObservations = 2;
+    // re-observation (new): a residual block enters through addFrame's one ZNCC test under the INITIAL pose; after pba_solve, and before
+    // the outlier passes (so that a cull judges the admitted blocks too), optimize() runs pba_admit then pba_solve again, up to
+    // reobservePasses times, and stops when a pass admits nothing.  Candidates are the (point, frame) pairs of the window that are not
+    // residual blocks and whose projection at the refined state lies inside addFrame's border with depth >= minValidDepth; one is taken
+    // when its loss-corrected cost is at most max(reobserveMinCost, reobserveFactor x the reobserveQuantile-quantile of the costs of the
+    // blocks the problem already has) (include/pba.h, pba_admit).  Every admitted block adds its frame to its scene point's visibility
+    // list, kept in ascending frame order: a point re-observed in the newest frame stays trackable under maxFrameDistance.  The last
+    // three are read only when reobservePasses > 0; their defaults are untuned on real imagery.  Ranges (else std::invalid_argument from
+    // the constructor): reobservePasses >= 0, reobserveQuantile in [0, 1], reobserveFactor >= 0 and finite, reobserveMinCost >= 0 and
+    // finite.  addFrames throws with reobservePasses > 0.  0: the class produces what it produced without the fields, and no new call
+    // reaches the engine.
+    int reobservePasses = 0;
+    double reobserveFactor = 1.0;
+    double reobserveQuantile = 0.5;
+    double reobserveMinCost = 0.0;
 
     Options() {}
     Options(const utils::ConfigFile& cf);
@@ -193,7 +213,13 @@ class PhotometricBundleAdjustment {
     // Options::outlierPasses: residual blocks and points the culls of this optimisation removed, summed over the passes.  initialCost is
     // then the FIRST solve's; finalCost, numSuccessfulStep, numResiduals, totalTime, message and iterationSummary are the LAST solve's
     int numCulledBlocks = 0, numCulledPoints = 0;
-    double totalTime = -1.0;                        // seconds
+    // Options::reobservePasses: residual blocks the admissions of this optimisation added, summed over the passes (the costs and the
+    // other fields follow the rule above: initialCost the FIRST solve's, the rest the LAST solve's)
+    int numAdmittedBlocks = 0;
+    // ... and which: (position of the scene point in visibilityLists() as it stands after this call, frame id) of every admitted block
+    // whose point is still held (the oldest frame's points have left by then), in the order of the admissions
+    std::vector<std::pair<uint32_t, uint32_t>> admittedBlocks;
+    double totalTime = -1.0;                       // seconds
     std::string message;
     std::vector<ceres::IterationSummary> iterationSummary;
     // Options::computeCovariance: blocks of (J^T J)^-1 at the refined state, unit residual variance (scale by your own sigma^2).
@@ -236,6 +262,7 @@ class PhotometricBundleAdjustment {
   bool optimizeAssemble(OptimizeState& st);
   void optimizeFinish(OptimizeState& st, Result* result);
   void cullAndResolve(OptimizeState& st);      // Options::outlierPasses, between the solve and optimizeFinish
+  void admitAndResolve(OptimizeState& st);     // Options::reobservePasses, between the solve and cullAndResolve
   typedef UniquePointer<ScenePoint> ScenePointPointer;
   typedef std::vector<ScenePointPointer> ScenePointPointerList;
 
