@@ -54,7 +54,7 @@ def _problem(radius, channels, seed):
 
 
 @pytest.mark.parametrize("channels", [1, 3, 8])
-@pytest.mark.parametrize("radius", [1, 2, 3])
+@pytest.mark.parametrize("radius", [1, 2, 3, 4, 5])
 def test_every_border_and_corner(radius, channels):
     p = _problem(radius, channels, seed=10 * radius + channels)
     lin = oracle.linearize(p, blocks=False)

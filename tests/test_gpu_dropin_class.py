@@ -59,11 +59,19 @@ def _read_results(path):
     return out
 
 
+def _aniso_k(pyramid=False):
+    """tests/asym_cases.py's fx != fy, cx != cy calibrations (120 x 160 images; in proportion for the pyramid's 160 x 224): the class takes
+    fx and fy apart in the back-projection z K^-1 [x y 1], in the visibility projection and in Calibration::pyrDown."""
+    import asym_cases
+    return asym_cases.PYRAMID_K if pyramid else asym_cases.ANISO_K
+
+
 @pytest.mark.timeout(900)
-def test_run_kitti_matches_emulated_reference_pipeline(tmp_path):
+@pytest.mark.parametrize("K", [(200.0, 200.0, 80.0, 60.0), _aniso_k()], ids=["fx-equals-fy", "anisotropic"])
+def test_run_kitti_matches_emulated_reference_pipeline(tmp_path, K):
     from oracle.frontend import Emulator
     assert os.path.exists(RUN), "build photobundle_amd/bin/run_kitti first (__graft_entry__.build())"
-    size, K = (120, 160), (200.0, 200.0, 80.0, 60.0)
+    size = (120, 160)
     n_frames, window, radius, max_points = 6, 4, 1, 4096  # no top-N cut: nth_element is unspecified among saliency ties
     tmp = str(tmp_path)
     imgs, depths, local = _write_sequence(tmp, n_frames, size, K)
@@ -119,10 +127,12 @@ def test_run_kitti_matches_emulated_reference_pipeline(tmp_path):
 
 
 @pytest.mark.timeout(1500)
-def test_pyramid_path_matches_emulation(tmp_path):
-    """configs[2] (photobundle_pyramid path): 2-level coarse-to-fine through run_kitti (numLevels = 2)."""
+@pytest.mark.parametrize("K", [(280.0, 280.0, 112.0, 80.0), _aniso_k(pyramid=True)], ids=["fx-equals-fy", "anisotropic"])
+def test_pyramid_path_matches_emulation(tmp_path, K):
+    """configs[2] (photobundle_pyramid path): 2-level coarse-to-fine through run_kitti (numLevels = 2).  The anisotropic K is the case that
+    sees Calibration::pyrDown halve fx and fy separately."""
     from oracle.frontend import PyramidEmulator
-    size, K = (160, 224), (280.0, 280.0, 112.0, 80.0)
+    size = (160, 224)
     n_frames, window, radius, max_points = 5, 3, 1, 100000
     tmp = str(tmp_path)
     imgs, depths, local = _write_sequence(tmp, n_frames, size, K)

@@ -30,12 +30,21 @@ def _symbolic_A(small_angle):
     return sp.lambdify(args, A, modules="mpmath"), sp.lambdify(args, sp.Matrix([u, v]), modules="mpmath")
 
 
-@pytest.mark.parametrize("small_angle", [False, True])
-def test_dual_number_rows_equal_the_symbolic_jacobian(small_angle):
+def _window(which):
+    if which == "asymmetric":      # fx != fy, cx != cy and patch weights without a symmetry (tests/asym_cases.py)
+        import asym_cases
+        return asym_cases.window("A4")
+    return synthetic.make_window(n_frames=4, n_points=60, radius=2, seed_offset=21, **SMALL)
+
+
+@pytest.mark.parametrize("small_angle,which", [pytest.param(False, "symmetric", id="False"), pytest.param(True, "symmetric", id="True"),
+                                               pytest.param(False, "asymmetric", id="asymmetric-False"),
+                                               pytest.param(True, "asymmetric", id="asymmetric-True")])
+def test_dual_number_rows_equal_the_symbolic_jacobian(small_angle, which):
     import mpmath
     mpmath.mp.dps = 40
     forms = {True: _symbolic_A(True), False: _symbolic_A(False)}
-    p = synthetic.make_window(n_frames=4, n_points=60, radius=2, seed_offset=21, **SMALL)
+    p = _window(which)
     cams = p.cams.copy()
     if small_angle:
         cams[:, :3] *= 1e-10          # theta^2 far below DBL_EPSILON: the first-order branch of the rotation
