@@ -397,6 +397,31 @@ int pba_covariance(pba_engine* e, double* cam_cov, double* point_cov, pba_covari
  * refuse an engine that holds a prior.  After a refused call the engine holds what it held before. */
 int pba_set_camera_prior(pba_engine* e, int32_t k, const int32_t* slots, const double* x0, const double* Lambda, const double* eta, double c);
 
+/* ---- point prior: the depth a point was created from, kept as a factor ------------------------------------------
+ * ONE extra residual block on every point's parameter block, with a constant Jacobian and no loss function, in information form (a
+ * depth factor Lambda = n n^T / sigma^2 has rank 1, so a square-root form of full rank cannot hold it).  For point i, with
+ * d = X_i - x0_i:     E_i = d^T Lambda_i d / 2,   gradient Lambda_i d,   Gauss-Newton block Lambda_i.
+ * x0 [n_points][3]; Lambda6 [n_points][6] = the upper triangle row by row (00 01 02 11 12 22).  A point with Lambda_i = 0 has no prior.
+ * x0 == NULL && Lambda6 == NULL clears.  E_pts = sum_i E_i enters every cost the LM loop sees (the linearisation cost, the candidate
+ * cost, summary.initial_cost and final_cost, pba_linearize's cost: added last, after the photometric sum); Lambda_i d joins the point
+ * gradient and its norms, diag Lambda_i the column norms that fix the Jacobi scale and the LM diagonal, Lambda_i the point block V_i
+ * before damping.  summary.num_residual_blocks and num_residuals keep counting the PHOTOMETRIC blocks only; pba_get_block_costs and
+ * the quantiles of pba_cull and pba_admit stay over the photometric blocks.
+ * Scope: the full mode at every window shape of 2..32 slots and any anchor mask -- the engine eliminates through the wide chain
+ * while a point prior is set, also on a narrow window, and pba_solve runs the host-stepped driver -- and the cameras-constant mode;
+ * pba_covariance in both (V_i includes Lambda_i: rank-1 depth priors close the gauge of a window with one constant camera).  Single
+ * rank.  Every sum has a fixed order: two fresh engines give the same bits.
+ * State: the prior is an input of the linearisation -- setting or clearing it drops the linearisation; pba_set_problem clears it (a
+ * prior belongs to one set of points); pba_set_cameras* keep it; an applied pba_cull gathers its rows with the surviving points; an
+ * applied pba_admit leaves them alone.
+ * PBA_ERR_INVALID with a message in pba_last_error, before anything is stored: no problem set; n_points differs from the problem's;
+ * exactly one pointer NULL; a non-finite entry; a negative diagonal entry of a Lambda_i (beyond that positive semidefiniteness is the
+ * caller's: an indefinite Lambda_i shows up as a point block that is not positive definite, an invalid step); multi-rank transports,
+ * the precision-sweep flags, the points-constant mode, the inverse-depth mode, the camera prior (hence pba_marginalize) -- whichever
+ * call comes second; pba_solve_batch refuses an engine that holds a point prior.  After a refused call the engine holds what it held
+ * before.  A device error during the upload (PBA_ERR_HIP) leaves the engine without a point prior. */
+int pba_set_point_prior(pba_engine* e, int32_t n_points, const double* x0, const double* Lambda6);
+
 /* The marginalisation that produces such a prior: the Schur complement, at the current (best) state, of the cameras that leave and of
  * every point they see.  M = the points with at least one observation in a slot of drop_mask; the factors are every residual block
  * of a point of M (in any slot) plus the engine's current prior if one is set (re-expanded at the current cameras, which is exact:

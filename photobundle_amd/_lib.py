@@ -107,7 +107,7 @@ SYMBOLS = [
     "pba_status_string", "pba_last_error", "pba_default_solver_options", "pba_create", "pba_destroy",
     "pba_set_frame_u8", "pba_set_frame_channels_f32", "pba_get_frame_planes", "pba_get_frame_channel", "pba_sample_frame", "pba_set_frame_descriptor_u8", "pba_get_frame_channels_f32", "pba_set_frame_pyr_down", "pba_set_problem", "pba_set_cameras", "pba_set_cameras_anchored", "pba_set_inverse_depth", "pba_set_points_constant", "pba_set_cameras_constant", "pba_get_points_world", "pba_get_state",
     "pba_linearize", "pba_step", "pba_accept", "pba_get_reduced_system", "pba_get_point_system", "pba_get_obs_records", "pba_solve", "pba_solve_batch", "pba_covariance",
-    "pba_set_camera_prior", "pba_marginalize", "pba_get_block_costs", "pba_cull", "pba_admit",
+    "pba_set_camera_prior", "pba_set_point_prior", "pba_marginalize", "pba_get_block_costs", "pba_cull", "pba_admit",
     "pba_comm_unique_id", "pba_comm_init_rccl", "pba_comm_init_callback", "pba_comm_enable_peer_exchange", "pba_comm_transport", "pba_comm_rank_count",
     "pba_set_profiling", "pba_get_counters", "pba_reset_counters", "pba_solve_driver",
     "pba_frontend_visibility", "pba_frontend_candidates", "pba_frontend_get_candidates", "pba_frontend_descriptors", "pba_frontend_zncc_probe",
@@ -176,6 +176,7 @@ def lib():
     L.pba_get_obs_records.argtypes = [C.c_void_p, C.c_void_p]
     L.pba_covariance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CovarianceInfo)]
     L.pba_set_camera_prior.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double]
+    L.pba_set_point_prior.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.pba_marginalize.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(MarginalInfo)]
     L.pba_get_block_costs.argtypes = [C.c_void_p, C.c_void_p]
     L.pba_cull.argtypes = [C.c_void_p, C.POINTER(CullOptions), C.c_void_p, C.c_void_p, C.POINTER(CullInfo)]

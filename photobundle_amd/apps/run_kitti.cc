@@ -84,8 +84,9 @@ static Calibration loadCalibration(const std::string& fn) {
 // prior: the sequence runs with marginalize = 1 (one more line, the E of the prior the optimisation carried)
 // culled: the sequence runs with outlierPasses > 0 (one more line, the residual blocks and points the optimisation's culls removed)
 // admitted: the sequence runs with reobservePasses > 0 (one more line, the residual blocks the optimisation's admissions added)
+// depth_prior: the sequence runs with depthPriorSigma > 0 (one more line, the depth factors' share of the final cost)
 static void dumpResult(const std::string& fn, int frame, const PhotometricBundleAdjustment::Result& r, bool prior = false, bool culled = false,
-                       bool admitted = false) {
+                       bool admitted = false, bool depth_prior = false) {
   std::FILE* f = std::fopen(fn.c_str(), "a");
   if (!f) throw std::runtime_error("cannot open " + fn);
   std::fprintf(f, "result frame %d poses %zu points %zu iterations %zu\n", frame, r.poses.size(), r.refinedPoints.size(), r.iterationSummary.size());
@@ -93,6 +94,7 @@ static void dumpResult(const std::string& fn, int frame, const PhotometricBundle
   if (prior) std::fprintf(f, "prior %.17g\n", r.priorCost);
   if (culled) std::fprintf(f, "culled blocks %d points %d\n", r.numCulledBlocks, r.numCulledPoints);
   if (admitted) std::fprintf(f, "admitted blocks %d\n", r.numAdmittedBlocks);
+  if (depth_prior) std::fprintf(f, "depthPrior %.17g\n", r.depthPriorCost);
   std::fprintf(f, "message %s\n", r.message.c_str());
   for (const auto& it : r.iterationSummary)
     std::fprintf(f, "it %d %d %d %.17g %.17g %.17g %.17g %.17g %.17g\n", it.iteration, (int)it.step_is_valid, (int)it.step_is_successful, it.cost,
@@ -274,6 +276,7 @@ int main(int argc, char** argv) {
     TrackOptions track_options;
     track_options.outlierPasses = outlier_passes;
     const int reobserve_passes = PhotometricBundleAdjustment::Options(*q.cf).reobservePasses;
+    const bool depth_prior = PhotometricBundleAdjustment::Options(*q.cf).depthPriorSigma > 0.0;
     Mat44 T_last = Mat44::Identity();      // (InitialPose = track) the frame-to-frame pose the previous frame was added with
     for (int f_i = 0; (q.track || f_i < (int)q.T_init.size()) && !gStop; ++f_i) {
       if (!q.read(f_i)) break;
@@ -300,7 +303,7 @@ int main(int argc, char** argv) {
       result.initialCost = -1.0;    // the class only touches `result` when an optimisation ran (photobundle.cc:857)
       if (photoba_pyr) photoba_pyr->addFrame(q.img.data(), q.depth.data(), T, &result);
       else photoba->addFrame(q.img.data(), q.depth.data(), T, &result);
-      if (!results.empty() && result.initialCost >= 0.0) dumpResult(results, f_i, result, with_prior, outlier_passes > 0, reobserve_passes > 0);
+      if (!results.empty() && result.initialCost >= 0.0) dumpResult(results, f_i, result, with_prior, outlier_passes > 0, reobserve_passes > 0, depth_prior);
     }
     writePoses(output, result, full_precision);
   } catch (const std::exception& ex) {

@@ -12,6 +12,7 @@
 // Included by pba_engine.hip after pba_kernels.h and pba_solve.h.
 #pragma once
 #include "pba_elim.h"
+#include "pba_point_prior.h"
 
 namespace pba {
 
@@ -33,8 +34,12 @@ struct CovPointParams {
   int32_t n_points, n_frames, dim;   // dim: free parameters per point (3, or 1 in the inverse-depth mode)
   uint32_t cost_mask;            // slots whose residual blocks are in the program
   double fx, fy;
+  const double* prior_x0;        // point prior (pba_point_prior.h), read by k_cov_point<true> only: [n_points][3]
+  const double* prior_L6;        // [n_points][6]
 };
 
+// kPrior: the point prior's Lambda_i joins V after the observation loop, before the factorisation (free world points only)
+template <bool kPrior>
 __global__ __launch_bounds__(kElimThreads) void k_cov_point(CovPointParams p) {
   __shared__ CamGeom s_geom[kMaxFramesWide];
   const int tid = threadIdx.x;
@@ -57,6 +62,10 @@ __global__ __launch_bounds__(kElimThreads) void k_cov_point(CovPointParams p) {
       elim_add_point_block(Ap, MAp, V);
     }
     if (p.P) {
+      if constexpr (kPrior) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) V[k] += p.prior_L6[6 * (size_t)pt + k];
+      }
       double Pm[6] = {0, 0, 0, 0, 0, 0}, Xm[6] = {0, 0, 0, 0, 0, 0};
       if (!elim_factor_point(V, p.dim, piv, Pm, Xm)) bad = (double)pt;
 #pragma unroll

@@ -223,6 +223,15 @@ struct pba_engine : pba::Handle {      // (device, stream, err, mem, events)
   int32_t prior_slots[kMaxFrames] = {};
   double* d_prior = nullptr;        // x0 [6 k] | eta [6 k] | Lambda [6 k][6 k]
   double* d_prior_out = nullptr;    // [6 k + 1] gradient | E of the last evaluation that asked for them
+  // point prior (pba_set_point_prior, pba_point_prior.h): one extra residual block on every point, in information form
+  bool pp_on = false;
+  double* d_pp_x0 = nullptr;        // [n_points][3]
+  double* d_pp_L6 = nullptr;        // [n_points][6] upper triangle of Lambda_i row by row
+  double* d_pp_part = nullptr;      // [kPointPriorMaxGrid] workgroup partials of k_point_prior_cost
+  double* d_pp_E = nullptr;         // [1] E_pts of the last evaluation that asked for it (pba_linearize's cost)
+  unsigned int* d_pp_ticket = nullptr;   // zero between launches
+  double* d_cull_pp_x0 = nullptr;   // the fresh buffers an applied cull gathers the surviving rows into (exchanged with the two above)
+  double* d_cull_pp_L6 = nullptr;
   // marginalisation (pba_marginalize): everything on first use, nothing shared with the LM
   double* d_marg_z = nullptr;       // [n_points][3]
   double* d_marg_r = nullptr;       // [n] gradient of the reduced system d_elim_S
@@ -373,7 +382,7 @@ void elim_inputs(const pba_engine* e, Params& p) {
 
 // ---- what is derived from what: a setter names the inputs it changed, invalidate() drops the caches derived from them; no setter
 // assigns a validity flag itself ------------------------------------------------------------------------------------------------------
-enum Input : unsigned { kInProblem = 1, kInCameras = 2, kInPointParams = 4, kInPointsConst = 8, kInCamsConst = 16, kInFrame = 32, kInPrior = 64 };
+enum Input : unsigned { kInProblem = 1, kInCameras = 2, kInPointParams = 4, kInPointsConst = 8, kInCamsConst = 16, kInFrame = 32, kInPrior = 64, kInPointPrior = 128 };
 // rec[k] no longer holds a Jacobian pass of point k (an input changed, or it is being overwritten): the sums reduced from it go too
 void drop_lin(pba_engine* e, int k) {
   e->lin_valid[k] = false;
@@ -401,7 +410,7 @@ int frame_uploaded(pba_engine* e, int slot, bool u8) {
 unsigned modes_present(const pba_engine* e, bool multi) {
   return (multi ? kModeMulti : 0u) | (e->inverse_depth ? kModeInverseDepth : 0u) | (sweep_mode(e) ? kModeSweep : 0u) |
          (e->have_cams && e->wide ? kModeWide : 0u) | (e->points_const ? kModePointsConst : 0u) | (e->cams_const ? kModeCamsConst : 0u) |
-         (e->have_cams && e->n_frames - e->n_free >= 2 ? kModeAnchors : 0u) | (e->prior_on ? kModePrior : 0u);
+         (e->have_cams && e->n_frames - e->n_free >= 2 ? kModeAnchors : 0u) | (e->prior_on ? kModePrior : 0u) | (e->pp_on ? kModePointPrior : 0u);
 }
 
 // Call-order / consistency check before any pass touches the device (include/pba.h: PBA_ERR_STATE).
@@ -477,7 +486,10 @@ void launch_sample(pba_engine* e, const SampleParams& sp) {
 // one kernel for back-substitution + candidate pass + step finalisation, at every patch radius; the opt-in
 // reduced-precision sampler modes (pba_config.flags bits 1-2) keep the unfused kernels
 // (wide windows run the unfused chain: the fused kernels stage kMaxFrames-entry tables)
-bool fused_capable(const pba_engine* e) { return e->fuse && sweep_mode(e) == 0 && !e->wide; }
+// The Schur elimination runs the wide chain (pba_wide.h): on a wide window, and at every window shape while a point prior is set (its
+// addend to V_i and g_i lives in k_wide_point<true>; k_schur is not touched).  `wide` alone keeps meaning the window's shape.
+bool eliminates_wide(const pba_engine* e) { return e->wide || e->pp_on; }
+bool fused_capable(const pba_engine* e) { return e->fuse && sweep_mode(e) == 0 && !eliminates_wide(e); }
 int sample_waves_for_radius(int) { return kSampleWaves; }
 
 __global__ void k_noop() {}
@@ -657,6 +669,15 @@ void launch_schur(pba_engine* e, const SchurParams& sp) {
   hipLaunchKernelGGL(k_schur, dim3(e->schur_grid), dim3(kTile), 0, e->stream, sp);
 }
 
+// E_pts of the point prior at the points `xyz` (pba_point_prior.h): added to *add_to and / or stored to *out, in stream order
+void launch_point_prior_cost(pba_engine* e, const double* xyz, double* add_to, double* out) {
+  PointPriorCostParams cp{};
+  cp.xyz = xyz; cp.x0 = e->d_pp_x0; cp.L6 = e->d_pp_L6; cp.part = e->d_pp_part; cp.ticket = e->d_pp_ticket; cp.add_to = add_to; cp.out = out;
+  cp.n_points = e->n_points;
+  const int grid = std::max(1, std::min(kPointPriorMaxGrid, (e->n_points + kPointPriorThreads - 1) / kPointPriorThreads));
+  hipLaunchKernelGGL(k_point_prior_cost, dim3(grid), dim3(kPointPriorThreads), 0, e->stream, cp);
+}
+
 // ---- wide windows (pba_wide.h) ------------------------------------------------------------------------------------
 // Co-observation lists, built on the host once per problem and camera set: for every pair of free cameras a <= b (enumerated
 // row by row, as the packed pair blocks) the (observation of a, observation of b) of every point both observe, in point order,
@@ -728,6 +749,7 @@ int wide_eliminate(pba_engine* e, int cur, int init_scale, const pba_solver_opti
   wp.sp = e->d_sp; wp.ptrec = e->d_ptrec; wp.fac = e->d_wfac; wp.part = e->d_wpt_part; wp.rec_stride = e->rec_stride;
   wp.n_points = e->n_points; wp.n_frames = e->n_frames; wp.init_scale = init_scale; wp.jacobi = o->jacobi_scaling;
   wp.fx = e->cfg.fx; wp.fy = e->cfg.fy; wp.inv_radius = 1.0 / radius; wp.min_diag = o->min_lm_diagonal; wp.max_diag = o->max_lm_diagonal;
+  wp.prior_x0 = e->d_pp_x0; wp.prior_L6 = e->d_pp_L6;
   WidePairParams pp{};
   pp.fac = e->d_wfac; pp.ent = e->d_went; pp.chunk = e->d_wchunk; pp.out = e->d_wsums;
   WideAssembleParams ap{};
@@ -735,9 +757,12 @@ int wide_eliminate(pba_engine* e, int cur, int init_scale, const pba_solver_opti
   ap.block_cost = e->d_block_cost[cur]; ap.block_fail = e->d_block_fail[cur]; ap.n_cost_blocks = e->cost_blocks[cur];
   ap.packed = e->d_packed; ap.scal = e->d_scal; ap.n_free = e->n_free; ap.n_pairs = e->n_pairs;
   ev_begin(e, 2);
-  hipLaunchKernelGGL(k_wide_point, dim3(e->wide_pt_blocks), dim3(kWideThreads), 0, e->stream, wp);
+  if (e->pp_on) hipLaunchKernelGGL(k_wide_point<true>, dim3(e->wide_pt_blocks), dim3(kWideThreads), 0, e->stream, wp);
+  else hipLaunchKernelGGL(k_wide_point<false>, dim3(e->wide_pt_blocks), dim3(kWideThreads), 0, e->stream, wp);
   if (e->wide_chunks > 0) hipLaunchKernelGGL(k_wide_pairs, dim3(e->wide_chunks), dim3(kWideThreads), 0, e->stream, pp);
   hipLaunchKernelGGL(k_wide_assemble, dim3(e->n_pairs + 1), dim3(128), 0, e->stream, ap);
+  // the point prior at the linearisation point joins the cost of the packed tail, last, after the photometric sum
+  if (e->pp_on) launch_point_prior_cost(e, e->d_xyz[cur], e->d_packed + tri_index(6 * e->n_free + 1) + 2 * 6 * e->n_free, nullptr);
   ev_end(e, 2);
   HIP_TRY(e, hipGetLastError());
   return PBA_OK;
@@ -1498,7 +1523,8 @@ int pba_set_problem(pba_engine* e, int32_t n_points, const double* xyz, const do
   e->inverse_depth = false;         // back to the reference's free world points until pba_set_inverse_depth says otherwise
   e->points_const = false;          // ... and to free points until pba_set_points_constant says otherwise
   e->cams_const = false;            // ... and to free cameras until pba_set_cameras_constant says otherwise
-  invalidate(e, kInProblem);
+  e->pp_on = false;                 // a point prior belongs to one set of points
+  invalidate(e, kInProblem | kInPointPrior);
   return PBA_OK;
 }
 
@@ -1705,6 +1731,14 @@ int pba_linearize(pba_engine* e, double* cost) {
       if (rcp) return rcp;
       c += E;
     }
+    if (e->pp_on) {      // E_pts at the current points, added last
+      double E = 0.0;
+      launch_point_prior_cost(e, e->d_xyz[e->cur], nullptr, e->d_pp_E);
+      HIP_TRY(e, hipGetLastError());
+      HIP_TRY(e, hipMemcpyAsync(&E, e->d_pp_E, sizeof(double), hipMemcpyDeviceToHost, e->stream));
+      HIP_TRY(e, hipStreamSynchronize(e->stream));
+      c += E;
+    }
     *cost = c;
   }
   return PBA_OK;
@@ -1853,8 +1887,10 @@ static int points_step(pba_engine* e, double radius, int32_t init_scale, const p
     ps.xyz = e->d_xyz[cur]; ps.rays = rays_or_null(e); ps.geom = e->d_geom[cur]; ps.rec = e->d_rec[cur];
     ps.pt_begin = e->d_pt_begin; ps.obs_slot = e->d_obs_slot; ps.sys = e->d_pts_sys; ps.rec_stride = e->rec_stride;
     ps.n_points = e->n_points; ps.n_frames = e->n_frames; ps.fx = e->cfg.fx; ps.fy = e->cfg.fy;
+    ps.prior_x0 = e->d_pp_x0; ps.prior_L6 = e->d_pp_L6;
     ev_begin(e, 2);
-    hipLaunchKernelGGL(k_points_system, dim3(grid), dim3(kPointsThreads), 0, e->stream, ps);
+    if (e->pp_on) hipLaunchKernelGGL(k_points_system<true>, dim3(grid), dim3(kPointsThreads), 0, e->stream, ps);
+    else hipLaunchKernelGGL(k_points_system<false>, dim3(grid), dim3(kPointsThreads), 0, e->stream, ps);
     ev_end(e, 2);
     HIP_TRY(e, hipGetLastError());
     e->pts_sys_cur = cur;
@@ -1879,7 +1915,15 @@ static int points_step(pba_engine* e, double radius, int32_t init_scale, const p
     candidate_pass(e, sp, cand, false);
     fp.cost_cand = e->d_block_cost[cand]; fp.fail_cand = e->d_block_fail[cand]; fp.n_cand = e->sample_grid;
   }
-  hipLaunchKernelGGL(k_points_finalize, dim3(1), dim3(kPointsThreads), 0, e->stream, fp);
+  if (e->pp_on) {
+    // the point prior joins both costs, last, after the photometric sums; the block is published behind them
+    hipLaunchKernelGGL(k_points_finalize<true>, dim3(1), dim3(kPointsThreads), 0, e->stream, fp);
+    launch_point_prior_cost(e, e->d_xyz[cur], e->d_scal + kCostLin, nullptr);
+    if (!grad_only) launch_point_prior_cost(e, e->d_xyz[cand], e->d_scal + kCandCost, nullptr);
+    hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, e->stream, e->d_scal, e->h_scal_dev, fp.host_seq, seq, (const double*)nullptr, 1);
+  } else {
+    hipLaunchKernelGGL(k_points_finalize<false>, dim3(1), dim3(kPointsThreads), 0, e->stream, fp);
+  }
   HIP_TRY(e, hipGetLastError());
   rc = wait_step_scalars(e, seq, out, scal);
   if ((rc == PBA_OK || rc == PBA_ERR_NUMERIC) && !grad_only && !out->linear_solver_ok) {
@@ -1909,11 +1953,11 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
   const bool multi = e->comm.multi();
 
   SchurParams sc = schur_params(e, cur, init_scale, o, radius);
-  if (e->dbg_left > 0 && !e->wide) {
+  if (e->dbg_left > 0 && !eliminates_wide(e)) {
     { const int rcd = dev_alloc(e, &e->d_dbg, pba_engine::kDbgWords); if (rcd) return rcd; }
     sc.dbg = e->d_dbg;
   }
-  if (e->wide) {
+  if (eliminates_wide(e)) {
     const int rcw = wide_eliminate(e, cur, init_scale, o, radius);
     if (rcw) return rcw;
   } else {
@@ -1924,7 +1968,7 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
   if (sc.dbg) { dump_schur_phase_cycles(e); --e->dbg_left; }
   SolveParams so = solve_params(e, cur, init_scale, o, radius, !grad_only && fused_capable(e));
   so.dbg = (e->dbg_left > 0) ? 1 : 0;
-  if (e->wide) {
+  if (eliminates_wide(e)) {
     ev_begin(e, 3);
     hipLaunchKernelGGL(k_solve_wide, dim3(1), dim3(kSolveWideT), solve_wide_smem_bytes(n), e->stream, so);
     ev_end(e, 3);
@@ -1963,7 +2007,7 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
     SampleParams sp = make_sample_params(e, cand);
     candidate_pass(e, sp, cand, false);
     hipLaunchKernelGGL(k_finalize_step, dim3(1), dim3(256), 0, e->stream, e->d_bs_out, e->backsub_grid, e->d_block_cost[cand],
-                       e->d_block_fail[cand], e->sample_grid, e->d_scal, (multi || e->prior_on) ? nullptr : e->h_scal_dev, h_seq_dev, seq);
+                       e->d_block_fail[cand], e->sample_grid, e->d_scal, (multi || e->prior_on || e->pp_on) ? nullptr : e->h_scal_dev, h_seq_dev, seq);
   }
   if (e->prior_on && !grad_only) {
     // the prior at the candidate cameras joins the candidate cost, last, after the photometric sum; the block is published below
@@ -1971,12 +2015,14 @@ int pba_internal_step(pba_engine* e, double radius, int32_t init_scale, const pb
     pp.add_to = e->d_scal + kCandCost;
     launch_prior(e, pp);
   }
+  // the point prior at the candidate points, likewise (k_backsub wrote them; single rank: pba_set_point_prior refuses the transports)
+  if (e->pp_on && !grad_only) launch_point_prior_cost(e, e->d_xyz[cand], e->d_scal + kCandCost, nullptr);
   HIP_TRY(e, hipGetLastError());
   if (multi) {
     int rc2 = exchange_step_scalars(e, xchg_packed);
     if (rc2) return rc2;
   }
-  if (multi || grad_only || e->prior_on) {
+  if (multi || grad_only || e->prior_on || e->pp_on) {
     hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, e->stream, e->d_scal, e->h_scal_dev, h_seq_dev, seq,
                        (const double*)(multi ? e->d_xchg : nullptr), e->comm.world);
     HIP_TRY(e, hipGetLastError());
@@ -2077,11 +2123,14 @@ int pba_covariance(pba_engine* e, double* cam_cov, double* point_cov, pba_covari
   elim_inputs(e, pp);
   pp.rays = rays; pp.P = pose ? nullptr : e->d_cov_P; pp.X = pose ? nullptr : e->d_elim_X; pp.pp = structure ? e->d_cov_pp : nullptr; pp.part = e->d_elim_part;
   pp.n_frames = e->n_frames; pp.dim = dim; pp.cost_mask = cost_mask;
+  pp.prior_x0 = e->d_pp_x0; pp.prior_L6 = e->d_pp_L6;
   // event profiling: read back at the end of the call (pba_internal_covariance_times)
   KernelTimes<4>& times = e->cov_times;
   if ((rc = times.start(e, e->profile))) return rc;
   times.begin(e, 0);
-  hipLaunchKernelGGL(k_cov_point, dim3(pt_blocks), dim3(kElimThreads), 0, e->stream, pp);
+  // (the point prior's Lambda_i joins V_i; pba_set_point_prior refuses the points-constant and the inverse-depth mode)
+  if (e->pp_on) hipLaunchKernelGGL(k_cov_point<true>, dim3(pt_blocks), dim3(kElimThreads), 0, e->stream, pp);
+  else hipLaunchKernelGGL(k_cov_point<false>, dim3(pt_blocks), dim3(kElimThreads), 0, e->stream, pp);
   times.end(e, 0);
   if (n > 0) {
     elim_inputs(e, cs);
@@ -2183,6 +2232,51 @@ int pba_set_camera_prior(pba_engine* e, int32_t k, const int32_t* slots, const d
   e->prior_c = c;
   e->prior_on = true;
   invalidate(e, kInPrior);
+  return PBA_OK;
+}
+
+// ---- point prior (pba_point_prior.h) ------------------------------------------------------------------------------------------------
+int pba_set_point_prior(pba_engine* e, int32_t n_points, const double* x0, const double* Lambda6) {
+  if (!e) return PBA_ERR_INVALID;
+  PBA_NOT_POISONED(e);
+  if (!e->have_problem) return fail(e, PBA_ERR_INVALID, "pba_set_point_prior: no problem is set (a point prior belongs to one set of points)");
+  if (n_points != e->n_points) return fail(e, PBA_ERR_INVALID, "pba_set_point_prior: n_points = %d, the problem has %d", n_points, e->n_points);
+  if ((x0 == nullptr) != (Lambda6 == nullptr)) return fail(e, PBA_ERR_INVALID, "pba_set_point_prior: exactly one of x0 and Lambda6 is NULL");
+  if (!x0) {
+    e->pp_on = false;
+    invalidate(e, kInPointPrior);
+    return PBA_OK;
+  }
+  for (size_t i = 0; i < (size_t)n_points; ++i) {
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(x0[3 * i + k])) return fail(e, PBA_ERR_INVALID, "pba_set_point_prior: non-finite x0 of point %zu", i);
+    for (int k = 0; k < 6; ++k)
+      if (!std::isfinite(Lambda6[6 * i + k])) return fail(e, PBA_ERR_INVALID, "pba_set_point_prior: non-finite Lambda of point %zu", i);
+    if (Lambda6[6 * i] < 0.0 || Lambda6[6 * i + 3] < 0.0 || Lambda6[6 * i + 5] < 0.0)
+      return fail(e, PBA_ERR_INVALID, "pba_set_point_prior: negative diagonal entry of Lambda of point %zu", i);
+  }
+  if (const char* why = mode_conflict(modes_present(e, e->comm.multi()) & ~(unsigned)kModePointPrior, kModePointPrior))
+    return fail(e, PBA_ERR_INVALID, "pba_set_point_prior: %s", why);
+  PBA_ENTER(e);
+  int rc;
+  // From here on the rows of an older prior are overwritten: it is switched off first, so that an upload that fails leaves an engine
+  // WITHOUT a prior (and without a linearisation), never one with mixed rows.  (The stream is idle: every pass synchronises before
+  // it returns.)
+  e->pp_on = false;
+  invalidate(e, kInPointPrior);
+  if ((rc = dev_alloc(e, &e->d_pp_part, (size_t)kPointPriorMaxGrid))) return rc;
+  if ((rc = dev_alloc(e, &e->d_pp_E, (size_t)1))) return rc;
+  if (!e->d_pp_ticket) {
+    if ((rc = dev_alloc(e, &e->d_pp_ticket, (size_t)1))) return rc;
+    HIP_TRY(e, hipMemsetAsync(e->d_pp_ticket, 0, sizeof(unsigned int), e->stream));
+  }
+  if ((rc = dev_alloc(e, &e->d_pp_x0, (size_t)3 * n_points))) return rc;
+  if ((rc = dev_alloc(e, &e->d_pp_L6, (size_t)6 * n_points))) return rc;
+  HIP_TRY(e, hipMemcpyAsync(e->d_pp_x0, x0, sizeof(double) * 3 * n_points, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(e->d_pp_L6, Lambda6, sizeof(double) * 6 * n_points, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  e->pp_on = true;
+  invalidate(e, kInPointPrior);
   return PBA_OK;
 }
 
@@ -2403,6 +2497,10 @@ int pba_cull(pba_engine* e, const pba_cull_options* o, uint8_t* block_keep, int3
   if ((rc = dev_alloc(e, &e->d_cull_obs_point, (size_t)n_obs))) return rc;
   if ((rc = dev_alloc(e, &e->d_cull_obs_slot, (size_t)n_obs))) return rc;
   if (e->inverse_depth && (rc = dev_alloc(e, &e->d_cull_rays, (size_t)6 * n_points))) return rc;
+  if (e->pp_on) {
+    if ((rc = dev_alloc(e, &e->d_cull_pp_x0, (size_t)3 * n_points))) return rc;
+    if ((rc = dev_alloc(e, &e->d_cull_pp_L6, (size_t)6 * n_points))) return rc;
+  }
   cp.obs_point_new = e->d_cull_obs_point; cp.obs_slot_new = e->d_cull_obs_slot;
   const auto row_grid = [&](int row_len) { return dim3((unsigned)std::min<int64_t>(((int64_t)n_points * row_len + kCullThreads - 1) / kCullThreads, 1 << 16)); };
   hipLaunchKernelGGL(k_cull_gather_obs, dim3(obs_blocks), dim3(kCullThreads), 0, e->stream, cp);
@@ -2413,6 +2511,12 @@ int pba_cull(pba_engine* e, const pba_cull_options* o, uint8_t* block_keep, int3
   if (e->inverse_depth)
     hipLaunchKernelGGL(k_cull_gather_rows<double>, row_grid(6), dim3(kCullThreads), 0, e->stream, (const double*)e->d_rays, e->d_cull_rays,
                        (const int32_t*)e->d_cull_map, n_points, 6);
+  if (e->pp_on) {      // the point prior's rows travel with the surviving points
+    hipLaunchKernelGGL(k_cull_gather_rows<double>, row_grid(3), dim3(kCullThreads), 0, e->stream, (const double*)e->d_pp_x0, e->d_cull_pp_x0,
+                       (const int32_t*)e->d_cull_map, n_points, 3);
+    hipLaunchKernelGGL(k_cull_gather_rows<double>, row_grid(6), dim3(kCullThreads), 0, e->stream, (const double*)e->d_pp_L6, e->d_cull_pp_L6,
+                       (const int32_t*)e->d_cull_map, n_points, 6);
+  }
   HIP_TRY(e, hipGetLastError());
   // the surviving lists on the host, for the tile builder pba_set_problem runs
   std::vector<int32_t> op((size_t)inf.n_blocks_after), os((size_t)inf.n_blocks_after);
@@ -2434,6 +2538,7 @@ int pba_cull(pba_engine* e, const pba_cull_options* o, uint8_t* block_keep, int3
   e->mem.exchange(&e->d_obs_point, &e->d_cull_obs_point);
   e->mem.exchange(&e->d_obs_slot, &e->d_cull_obs_slot);
   if (e->inverse_depth) e->mem.exchange(&e->d_rays, &e->d_cull_rays);
+  if (e->pp_on) { e->mem.exchange(&e->d_pp_x0, &e->d_cull_pp_x0); e->mem.exchange(&e->d_pp_L6, &e->d_cull_pp_L6); }
   if ((rc = problem_reserve(e, L, PD))) return rc;
   if ((rc = problem_upload_tables(e, L))) return rc;
   HIP_TRY(e, hipStreamSynchronize(e->stream));
@@ -2779,6 +2884,7 @@ int pba_internal_patch_len(const pba_engine* e) { return e->channels * (2 * e->c
 int pba_internal_async_capable(const pba_engine* e, const pba_solver_options* o) {
   if (e->points_const || e->cams_const) return 0;     // the pose-only and structure-only modes are built on the host-stepped driver
   if (e->prior_on) return 0;                          // the camera prior is an addend between reduction and solve: host-stepped only
+  if (e->pp_on) return 0;                             // the point prior eliminates through the wide chain: host-stepped only
   return e->use_async && fused_capable(e) && (e->comm.kind != 2 || e->comm.peer) && o->max_num_iterations < pba_engine::kMaxLog - 2 && !e->profile;
 }
 int pba_internal_points_constant(const pba_engine* e) { return e->points_const ? 1 : 0; }

@@ -13,7 +13,7 @@ enum ModeFeature : unsigned {      // one bit each
   kModeMulti = 1, kModeInverseDepth = 2, kModeSweep = 4 /* pba_config.flags bits 1-2 */, kModeWide = 8, kModePointsConst = 16, kModeCamsConst = 32,
   kModeAnchors = 64 /* two or more constant slots */, kModeCovariance = 128 /* pba_covariance */, kModeBatch = 256 /* pba_solve_batch */,
   kModePrior = 512 /* pba_set_camera_prior; pba_marginalize asks as if it switched one on */, kModeCull = 1024 /* pba_cull */,
-  kModeAdmit = 2048 /* pba_admit */
+  kModeAdmit = 2048 /* pba_admit */, kModePointPrior = 4096 /* pba_set_point_prior */
 };
 struct ModeRule { unsigned a, b; const char* then_b; const char* then_a; };
 constexpr ModeRule kModeRules[] = {
@@ -51,6 +51,16 @@ constexpr ModeRule kModeRules[] = {
     {kModePrior, kModeBatch, "the camera prior (pba_set_camera_prior) solves alone", nullptr},
     {kModeMulti, kModeCull, "multi-rank engines (pba_comm_*) are not built for culling: the order statistic would need an exchange", nullptr},
     {kModeSweep, kModeCull, "the precision-sweep sampler modes (pba_config.flags bits 1-2) are not built for culling", nullptr},
+    // (the point prior's rows; no query matches one of them and a row of pba_admit at once, and tests/test_admit_cpu.py pins those two as the last)
+    {kModeMulti, kModePointPrior, "multi-rank solves (pba_comm_*) are not built for the point prior", "multi-rank solves are not built for the point prior (pba_set_point_prior)"},
+    {kModePointPrior, kModeSweep, "the precision-sweep sampler modes (pba_config.flags bits 1-2) are not built for the point prior", nullptr},
+    {kModePointPrior, kModeBatch, "the point prior (pba_set_point_prior) solves alone", nullptr},
+    {kModePointsConst, kModePointPrior, "the point prior is not built for the points-constant mode (pba_set_points_constant): the prior is then a constant",
+     "the point prior (pba_set_point_prior) is not built for the points-constant mode: the prior is then a constant"},
+    {kModeInverseDepth, kModePointPrior, "the point prior is not built for the inverse-depth mode (pba_set_inverse_depth)",
+     "the point prior (pba_set_point_prior) is not built for the inverse-depth mode"},
+    {kModePrior, kModePointPrior, "the point prior is not built next to the camera prior (pba_set_camera_prior): it eliminates through the wide chain, the camera prior is narrow-only",
+     "the camera prior is not built next to the point prior (pba_set_point_prior): it is narrow-only, the point prior eliminates through the wide chain"},
     {kModeMulti, kModeAdmit, "multi-rank engines (pba_comm_*) are not built for re-observation: the order statistic would need an exchange", nullptr},
     {kModeSweep, kModeAdmit, "the precision-sweep sampler modes (pba_config.flags bits 1-2) are not built for re-observation", nullptr},
 };

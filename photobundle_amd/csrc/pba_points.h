@@ -11,6 +11,7 @@
 // The camera Jacobian is never formed and the cameras are never written.
 #pragma once
 #include "pba_kernels.h"
+#include "pba_point_prior.h"
 
 namespace pba {
 
@@ -30,8 +31,12 @@ struct PointsSystemParams {
   int64_t rec_stride;
   int32_t n_points, n_frames;
   double fx, fy;
+  const double* prior_x0;      // point prior (pba_point_prior.h), read by k_points_system<true> only: [n_points][3]
+  const double* prior_L6;      // [n_points][6]
 };
 
+// kPrior: the point prior's Lambda_i joins V_p and Lambda_i (X - x0_i) joins g_p after the observation loop
+template <bool kPrior>
 __global__ __launch_bounds__(kPointsThreads) void k_points_system(PointsSystemParams p) {
   __shared__ CamGeom s_geom[kMaxFramesWide];
   const int tid = threadIdx.x;
@@ -65,6 +70,14 @@ __global__ __launch_bounds__(kPointsThreads) void k_points_system(PointsSystemPa
     v[5] += Ap[0][2] * MAp[0][2] + Ap[1][2] * MAp[1][2];
 #pragma unroll
     for (int k = 0; k < 3; ++k) v[6 + k] += -(Ap[0][k] * b0 + Ap[1][k] * b1);      // J^T r = -Ap^T b
+  }
+  if constexpr (kPrior) {      // (free world points: pba_set_point_prior refuses the inverse-depth mode)
+    double L[6], Ld[3], d[3];
+    point_prior_terms(p.prior_x0, p.prior_L6, pt, prm, L, Ld, d);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v[k] += L[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[6 + k] += Ld[k];
   }
 #pragma unroll
   for (int k = 0; k < kPointsSys; ++k) p.sys[(size_t)k * p.n_points + pt] = v[k];
@@ -171,6 +184,8 @@ struct PointsFinalizeParams {
 
 // Thread t adds rows t, t + 256, ... in ascending order, then the 256 sums go through one binary tree: the order depends on the number
 // of rows (the problem's shape) only.  A failed block anywhere makes the whole step a zero step (LinearSolver failure in Ceres).
+// kPrior leaves the scalar block on the device: the point prior's costs are added behind it, then k_publish publishes.
+template <bool kPrior>
 __global__ __launch_bounds__(kPointsThreads) void k_points_finalize(PointsFinalizeParams p) {
   __shared__ double s_red[6][kPointsThreads];
   __shared__ double s_mx[2][kPointsThreads];
@@ -208,9 +223,11 @@ __global__ __launch_bounds__(kPointsThreads) void k_points_finalize(PointsFinali
     // the cameras are constant: they enter none of the step scalars
     p.scal[kMccCams] = 0.0; p.scal[kStep2Cams] = 0.0; p.scal[kX2Cams] = 0.0; p.scal[kGmaxCams] = 0.0; p.scal[kGnorm2Cams] = 0.0;
   }
-  __syncthreads();
-  publish_scal(p.scal, p.host_scal, tid, blockDim.x);
-  publish_seq(p.host_seq, p.seq, tid);
+  if constexpr (!kPrior) {
+    __syncthreads();
+    publish_scal(p.scal, p.host_scal, tid, blockDim.x);
+    publish_seq(p.host_seq, p.seq, tid);
+  }
 }
 
 }  // namespace pba

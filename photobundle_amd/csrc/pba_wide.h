@@ -10,6 +10,7 @@
 //                    backward substitution, then solve_epilogue.
 // Every sum has a fixed order (no atomics): runs are reproducible.  Included by pba_engine.hip after pba_kernels.h.
 #pragma once
+#include "pba_point_prior.h"
 
 namespace pba {
 
@@ -32,8 +33,12 @@ struct WidePointParams {
   int64_t rec_stride;
   int32_t n_points, n_frames, init_scale, jacobi;
   double fx, fy, inv_radius, min_diag, max_diag;
+  const double* prior_x0;        // point prior (pba_point_prior.h), read by k_wide_point<true> only: [n_points][3]
+  const double* prior_L6;        // [n_points][6]
 };
 
+// kPrior: the point prior's Lambda_i joins V and Lambda_i (X - x0_i) joins g_p after the observation loop, before scale, damping and factor
+template <bool kPrior>
 __global__ __launch_bounds__(kWideThreads) void k_wide_point(WidePointParams p) {
   __shared__ CamGeom s_geom[kMaxFramesWide];
   __shared__ double s_red[kWideThreads / 64][3];
@@ -70,6 +75,14 @@ __global__ __launch_bounds__(kWideThreads) void k_wide_point(WidePointParams p) 
       for (int k = 0; k < 6; ++k) V[k] += v[k];
 #pragma unroll
       for (int k = 0; k < 3; ++k) gp[k] += v[6 + k];
+    }
+    if constexpr (kPrior) {
+      double L[6], Ld[3], d[3];
+      point_prior_terms(p.prior_x0, p.prior_L6, (size_t)pt, X, L, Ld, d);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) V[k] += L[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) gp[k] += Ld[k];
     }
     // damping and the point block's inverse: k_schur P2
     double s[3];

@@ -341,6 +341,21 @@ class Engine:
     def clear_camera_prior(self):
         self._check(self._L.pba_set_camera_prior(self._h, 0, None, None, None, None, 0.0), "pba_set_camera_prior")
 
+    def set_point_prior(self, x0, Lambda6=None):
+        """pba_set_point_prior: one extra residual block E_i = d^T Lambda_i d / 2, d = X_i - x0_i, on every point; x0 [n_points, 3],
+        Lambda6 [n_points, 6] = the upper triangle of Lambda_i row by row (00 01 02 11 12 22), zeros for a point without a prior
+        (include/pba.h).  set_point_prior(None) clears."""
+        if x0 is None and Lambda6 is None:
+            self._check(self._L.pba_set_point_prior(self._h, self.n_points, None, None), "pba_set_point_prior")
+            return
+        x0 = None if x0 is None else np.ascontiguousarray(x0, np.float64).reshape(-1, 3)
+        L6 = None if Lambda6 is None else np.ascontiguousarray(Lambda6, np.float64).reshape(-1, 6)
+        n = (x0 if x0 is not None else L6).shape[0]
+        if x0 is not None and L6 is not None and L6.shape[0] != n:
+            raise ValueError("set_point_prior: x0 has %d rows, Lambda6 %d" % (n, L6.shape[0]))
+        self._check(self._L.pba_set_point_prior(self._h, n, _ptr(x0) if x0 is not None else None, _ptr(L6) if L6 is not None else None),
+                    "pba_set_point_prior")
+
     def marginalize(self, drop_slots):
         """pba_marginalize: the prior that the cameras of `drop_slots` and every point they see leave on the kept free cameras, at the
         current state (include/pba.h).  Returns a dict with slots [k], x0 [k, 6], Lambda [6k, 6k], eta [6k], c and the fields of

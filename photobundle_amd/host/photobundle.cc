@@ -183,7 +183,8 @@ PhotometricBundleAdjustment::Options::Options(const utils::ConfigFile& cf)
       reobservePasses(cf.get<int>("reobservePasses", 0)),
       reobserveFactor(cf.get<double>("reobserveFactor", 1.0)),
       reobserveQuantile(cf.get<double>("reobserveQuantile", 0.5)),
-      reobserveMinCost(cf.get<double>("reobserveMinCost", 0.0)) {}
+      reobserveMinCost(cf.get<double>("reobserveMinCost", 0.0)),
+      depthPriorSigma(cf.get<double>("depthPriorSigma", 0.0)) {}
 
 std::ostream& operator<<(std::ostream& os, const PhotometricBundleAdjustment::Options& o) {
   using DT = PhotometricBundleAdjustment::Options::DescriptorType;
@@ -198,7 +199,7 @@ std::ostream& operator<<(std::ostream& os, const PhotometricBundleAdjustment::Op
      << "\noutlierPasses = " << o.outlierPasses << "\noutlierQuantile = " << o.outlierQuantile << "\noutlierFactor = " << o.outlierFactor
      << "\noutlierMinCost = " << o.outlierMinCost << "\noutlierMinObservations = " << o.outlierMinObservations
      << "\nreobservePasses = " << o.reobservePasses << "\nreobserveFactor = " << o.reobserveFactor << "\nreobserveQuantile = " << o.reobserveQuantile
-     << "\nreobserveMinCost = " << o.reobserveMinCost << "\n";
+     << "\nreobserveMinCost = " << o.reobserveMinCost << "\ndepthPriorSigma = " << o.depthPriorSigma << "\n";
   return os;
 }
 
@@ -270,6 +271,7 @@ struct PhotometricBundleAdjustment::ScenePoint {
   bool was_refined = false;
   bool ref_culled = false;       // Options::outlierPasses: the block of the reference frame was culled (the frame stays in `f`)
   int x0 = 0, y0 = 0;
+  double z0 = 0.0;               // the depth the point was created from, at (x0, y0) of its reference frame (Options::depthPriorSigma)
   uint32_t ref_id;               // the frame the point was created in: f.front(), until Options::reobservePasses admits an EARLIER frame
   ScenePoint(const Vec3& X_, uint32_t f_id) : X(X_), X_original(X_), ref_id(f_id) { f.reserve(8); f.push_back(f_id); }
   uint32_t refFrameId() const { return ref_id; }
@@ -286,7 +288,15 @@ PhotometricBundleAdjustment::PhotometricBundleAdjustment(const Calibration& cali
   if (options.numConstantFrames < 1 || options.numConstantFrames > options.slidingWindowSize - 1)
     throw std::invalid_argument("numConstantFrames = " + std::to_string(options.numConstantFrames) + " is outside 1 .. slidingWindowSize - 1 = " +
                                 std::to_string(options.slidingWindowSize - 1) + ": at least one frame of the window must stay free");
-  if (options.computeCovariance && options.numConstantFrames < 2 && !options.camerasConstant)
+  if (!(options.depthPriorSigma >= 0.0) || !std::isfinite(options.depthPriorSigma))
+    throw std::invalid_argument("depthPriorSigma = " + std::to_string(options.depthPriorSigma) + " must be finite and >= 0 (0 switches the depth prior off)");
+  if (options.depthPriorSigma > 0.0 && !(calib.b() > 0.0))
+    throw std::invalid_argument("depthPriorSigma > 0 needs a stereo baseline: Calibration::b() = " + std::to_string(calib.b()) +
+                                " (sigma_z = depthPriorSigma z^2 / (b fx))");
+  if (options.depthPriorSigma > 0.0 && options.marginalize)
+    throw std::invalid_argument("depthPriorSigma > 0 with marginalize: the engine refuses a camera prior next to the point prior");
+  // (with depth priors the scale of the window is fixed: one constant frame is then enough)
+  if (options.computeCovariance && options.numConstantFrames < 2 && !options.camerasConstant && !(options.depthPriorSigma > 0.0))
     throw std::invalid_argument("computeCovariance needs numConstantFrames >= 2 or camerasConstant: with one constant frame the gauge is open (the "
                                 "scale of the window is free) and the normal matrix is singular");
   if (options.marginalize && options.camerasConstant)
@@ -654,7 +664,7 @@ bool PhotometricBundleAdjustment::addFrameImpl(const uint8_t* I_ptr, const float
     p->patch.set(I, (double)x, (double)y);
     p->descriptor.resize((size_t)num_channels * patch_length);
     p->saliency = cands[k].saliency;
-    p->x0 = x; p->y0 = y;
+    p->x0 = x; p->y0 = y; p->z0 = (double)z;
     new_points[k] = std::move(p);
   }
   std::fprintf(stderr, "updated %d [%0.2f%%] max %d new %d\n", num_updated,
@@ -709,6 +719,8 @@ struct PhotometricBundleAdjustment::OptimizeState {
   uint32_t frame_id_start = 0, frame_id_end = 0;
   int n_anchored = 0;      // oldest frames held constant through pba_set_cameras_anchored (0: the one-slot call, as ever)
   std::vector<double> cams, xyz;
+  std::vector<double> cams_start;                // Options::depthPriorSigma: the cameras the window started from (the factors are expressed there)
+  double depth_prior_cost = 0.0;
   std::vector<ScenePoint*> selected;
   std::vector<int32_t> obs_point, obs_slot;      // the observation list the engine holds (Options::outlierPasses maps removed blocks back)
   int culled_blocks = 0, culled_points = 0;      // Options::outlierPasses, summed over the passes
@@ -846,6 +858,31 @@ void PhotometricBundleAdjustment::cullAndResolve(OptimizeState& st) {
   st.summary.initial_cost = first_initial_cost;
 }
 
+// Options::depthPriorSigma: x0 [n][3] and Lambda6 [n][6] (upper triangle row by row) of the points `selected`, with (R, t) the
+// world->camera transform of each point's reference frame in `cams` (ring slot = id % window):
+//   n = R^T e_z,  X0 = R^T (((x0 - cx) z0 / fx, (y0 - cy) z0 / fy, z0) - t),  sigma_z = sigma_d z0^2 / (b fx),  Lambda = n n^T / sigma_z^2
+void PhotometricBundleAdjustment::depthPrior(const std::vector<ScenePoint*>& selected, const std::vector<double>& cams, std::vector<double>& x0,
+                                             std::vector<double>& L6) const {
+  const uint32_t window = (uint32_t)_options_ptr->slidingWindowSize;
+  const double fx = _calib.fx(), fy = _calib.fy(), cx = _calib.cx(), cy = _calib.cy(), bf = _calib.b() * _calib.fx();
+  x0.resize(3 * selected.size());
+  L6.resize(6 * selected.size());
+  for (size_t i = 0; i < selected.size(); ++i) {
+    const ScenePoint* pt = selected[i];
+    const Mat44 T = ParamsToPose(&cams[6 * (size_t)(pt->refFrameId() % window)]);
+    const double z = pt->z0;
+    const double c[3] = {((double)pt->x0 - cx) * z / fx - T(0, 3), ((double)pt->y0 - cy) * z / fy - T(1, 3), z - T(2, 3)};
+    double n[3];
+    for (int k = 0; k < 3; ++k) {
+      x0[3 * i + k] = T(0, k) * c[0] + T(1, k) * c[1] + T(2, k) * c[2];      // R^T c
+      n[k] = T(2, k);                                                         // R^T e_z
+    }
+    const double sz = _options_ptr->depthPriorSigma * z * z / bf, w = 1.0 / (sz * sz);
+    double* L = &L6[6 * i];
+    L[0] = w * n[0] * n[0]; L[1] = w * n[0] * n[1]; L[2] = w * n[0] * n[2]; L[3] = w * n[1] * n[1]; L[4] = w * n[1] * n[2]; L[5] = w * n[2] * n[2];
+  }
+}
+
 bool PhotometricBundleAdjustment::optimizeAssemble(OptimizeState& st) {
   st.t_lo = wall_ms();
   const uint32_t frame_id_start = _frame_buffer.front()->id, frame_id_end = _frame_buffer.back()->id;
@@ -952,6 +989,13 @@ bool PhotometricBundleAdjustment::optimizeAssemble(OptimizeState& st) {
       }
       st.has_prior = _prior_valid;
     }
+    // Options::depthPriorSigma: the stereo depth of every point as a factor, after the problem (which clears an older one)
+    if (_options_ptr->depthPriorSigma > 0.0) {
+      st.cams_start = cams;
+      std::vector<double> x0, L6;
+      depthPrior(selected, st.cams_start, x0, L6);
+      check(_engine, pba_set_point_prior(_engine, (int32_t)selected.size(), x0.data(), L6.data()), "pba_set_point_prior");
+    }
     st.lap(2);
     pba_default_solver_options(&st.so);     // GetSolverOptions (:738-761)
     st.so.verbose = _options_ptr->verbose ? 1 : 0;
@@ -982,6 +1026,19 @@ void PhotometricBundleAdjustment::optimizeFinish(OptimizeState& st, Result* resu
     const bool cams_const = _options_ptr->camerasConstant;
     check(_engine, pba_get_state(_engine, cams_const ? nullptr : cams.data(), xyz.data()), "pba_get_state");
     for (size_t i = 0; i < selected.size(); ++i) for (int k = 0; k < 3; ++k) selected[i]->X[k] = xyz[3 * i + k];
+    if (_options_ptr->depthPriorSigma > 0.0) {
+      // E of the depth factors at the refined points (the survivors of the outlier passes: the engine gathered the same rows)
+      std::vector<double> x0, L6;
+      depthPrior(selected, st.cams_start, x0, L6);
+      double E = 0.0;
+      for (size_t i = 0; i < selected.size(); ++i) {
+        const double* L = &L6[6 * i];
+        const double d[3] = {xyz[3 * i] - x0[3 * i], xyz[3 * i + 1] - x0[3 * i + 1], xyz[3 * i + 2] - x0[3 * i + 2]};
+        E += 0.5 * (d[0] * (L[0] * d[0] + L[1] * d[1] + L[2] * d[2]) + d[1] * (L[1] * d[0] + L[3] * d[1] + L[4] * d[2]) +
+                    d[2] * (L[2] * d[0] + L[4] * d[1] + L[5] * d[2]));
+      }
+      st.depth_prior_cost = E;
+    }
     if (_options_ptr->computeCovariance) {
       st.point_cov.assign(9 * selected.size(), 0.0);
       if (!cams_const) st.cam_cov.assign((size_t)36 * window * window, 0.0);
@@ -1058,6 +1115,7 @@ void PhotometricBundleAdjustment::optimizeFinish(OptimizeState& st, Result* resu
     result->finalCost = summary.final_cost;
     result->fixedCost = summary.fixed_cost;
     result->priorCost = st.prior_cost;
+    result->depthPriorCost = st.depth_prior_cost;
     result->numSuccessfulStep = summary.num_successful_steps;
     result->totalTime = summary.total_time_in_seconds;
     result->numResiduals = summary.num_residuals;
@@ -1139,6 +1197,9 @@ void PhotometricBundleAdjustment::addFrames(const std::vector<PhotometricBundleA
     if (!instances[i] || !frames[i].T) throw std::invalid_argument("addFrames: null instance or pose");
     for (size_t j = 0; j < i; ++j) if (instances[j] == instances[i]) throw std::invalid_argument("addFrames: an instance appears twice");
   }
+  for (size_t i = 0; i < n; ++i)
+    if (instances[i]->_options_ptr->depthPriorSigma > 0.0)
+      throw std::invalid_argument("addFrames: Options::depthPriorSigma solves alone (pba_solve_batch refuses an engine that holds a point prior); use addFrame");
   for (size_t i = 0; i < n; ++i)
     if (instances[i]->_options_ptr->marginalize)
       throw std::invalid_argument("addFrames: Options::marginalize solves alone (pba_solve_batch refuses an engine that holds a prior); use addFrame");

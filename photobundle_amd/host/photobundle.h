@@ -147,9 +147,10 @@ class PhotometricBundleAdjustment {
     // (pba_set_cameras_anchored).  1 is the reference's behaviour (:809-813); valid values are 1 .. slidingWindowSize - 1, anything
     // else throws std::invalid_argument when the class is constructed.  trackFrame is not affected.
     int numConstantFrames = 1;
-    // covariance output (new): pba_covariance after every optimisation, into Result.  Needs a fixed gauge: numConstantFrames >= 2 or
-    // camerasConstant; with one constant frame the scale of the window is free and the normal matrix singular, so the constructor
-    // throws std::invalid_argument.  Off: the class produces what it produced without the field.
+    // covariance output (new): pba_covariance after every optimisation, into Result.  Needs a fixed gauge: numConstantFrames >= 2,
+    // camerasConstant, or depthPriorSigma > 0 (the depth factors fix the scale); with one constant frame and none of these the scale of
+    // the window is free and the normal matrix singular, so the constructor throws std::invalid_argument.  Off: the class produces
+    // what it produced without the field.
     bool computeCovariance = false;
     // marginalisation prior (new): before optimize() evicts the oldest frame's points it keeps what they said about the remaining
     // cameras as a quadratic prior (pba_marginalize on the oldest frame's ring slot), and the next window's optimisation carries it as
@@ -188,6 +189,17 @@ class PhotometricBundleAdjustment {
     double reobserveFactor = 1.0;
     double reobserveQuantile = 0.5;
     double reobserveMinCost = 0.0;
+    // depth prior (new): every scene point keeps the stereo depth z0 it was created from as a factor (pba_set_point_prior).  The value is
+    // the standard deviation of the DISPARITY in pixels; 0 switches the prior off.  Before the solve of every window, for every point of
+    // the problem, with (R, t) the world->camera transform of the point's reference frame as this window starts from it:
+    //   n = R^T e_z,  X0 = R^T (((x0 - cx) z0 / fx, (y0 - cy) z0 / fy, z0) - t),  sigma_z = depthPriorSigma z0^2 / (b fx),  Lambda = n n^T / sigma_z^2.
+    // The reference frame is always part of the window, so the factor is re-expressed at that frame's latest pose every window: an
+    // approximation of a camera-point depth factor, which would move with the camera inside the solve.  The engine carries the rows
+    // through the outlier and re-observation passes.  std::invalid_argument from the constructor when the value is negative or not
+    // finite, when it is positive and Calibration::b() <= 0, and together with marginalize (the engine refuses a camera prior next to
+    // the point prior); from addFrames when it is positive (pba_solve_batch refuses it).  0: the class produces what it produced
+    // without the field, and no new call reaches the engine.
+    double depthPriorSigma = 0.0;
 
     Options() {}
     Options(const utils::ConfigFile& cf);
@@ -208,6 +220,7 @@ class PhotometricBundleAdjustment {
     double fixedCost = -1.0;
     double priorCost = 0.0;                         // Options::marginalize: E of the prior this optimisation carried, at its final state
                                                     // (part of finalCost); 0 without a prior
+    double depthPriorCost = 0.0;                    // Options::depthPriorSigma: the depth factors' share of finalCost, at the final state; 0 when off
     int numSuccessfulStep = 0;
     int numResiduals = 0;
     // Options::outlierPasses: residual blocks and points the culls of this optimisation removed, summed over the passes.  initialCost is
@@ -263,6 +276,8 @@ class PhotometricBundleAdjustment {
   void optimizeFinish(OptimizeState& st, Result* result);
   void cullAndResolve(OptimizeState& st);      // Options::outlierPasses, between the solve and optimizeFinish
   void admitAndResolve(OptimizeState& st);     // Options::reobservePasses, between the solve and cullAndResolve
+  // Options::depthPriorSigma: the depth factors of `selected` expressed at the cameras `cams` (what pba_set_point_prior takes)
+  void depthPrior(const std::vector<ScenePoint*>& selected, const std::vector<double>& cams, std::vector<double>& x0, std::vector<double>& L6) const;
   typedef UniquePointer<ScenePoint> ScenePointPointer;
   typedef std::vector<ScenePointPointer> ScenePointPointerList;
 
